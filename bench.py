@@ -10,10 +10,23 @@ random-init weights of the reference architecture (model.py:204-281).
 
   python bench.py [--gpus N] [--steps K] [--warmup W]     (N>1: spawns N ranks itself)
   torchrun --nproc-per-node N bench.py --gpus N ...       (one rank per GPU, RCCL)
+  python bench.py ... --dump-outputs DIR                  (what the last timed step computed, as .npy)
+  python bench.py ... --full                              (+ roofline, CPU baselines, secondary legs)
 
 Prints ONE JSON line on rank 0.  `value` = frames/s over all ranks (weak
 scaling: 32 frames per GPU per step), timed over K steps with no per-launch
-instrumentation.  `roofline` is for the dominant kernel: a second pass of
+instrumentation; `ms_per_step` = the milliseconds one of those K steps took.  A
+plain run does only that: set up, W warm-up steps, the K timed steps, the
+optional dump, the line.  Everything below needs --full.
+
+--dump-outputs DIR writes, right after the K timed steps, what a caller of the
+timed path holds after the last one, as float32 DIR/<name>.npy (rank 0): for a
+training step the returned [loss, acc] (`loss_acc`), the flat parameter vector
+the step updated (`params`) and the BatchNorm moving statistics (`bufs`); for
+inference the predicted frames (`yhat`; above 48 MiB a fixed, seeded sample of its
+elements, so a dump stays under 64 MB).  Weights and inputs are seeded, so two builds can be compared file by file.
+
+`roofline` (--full) is for the dominant kernel: a second pass of
 min(K, 10) steps brackets every conv launch with HIP events on the stream it
 runs on (its ms/step is reported beside).  `allreduce_exposed` (N>1) is the time
 the compute stream waits for the RCCL buckets after backward.  `cpu_baseline`
@@ -46,7 +59,10 @@ F32_PEAK_TF = 157.3     # MI355X fp32 MFMA (= fp32 vector rate)
 HBM_PEAK_GBS = 8000.0
 
 
-def parse():
+DUMP_SAMPLE = 12 << 20  # elements kept of an output too large to dump whole (48 MiB of float32)
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -56,6 +72,11 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float32"])
     ap.add_argument("--mode", default="train", choices=["train", "infer"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the instrumented (roofline) pass, the CPU baselines, the replica check "
+                         "and the secondary legs; without it only the headline steps are run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-scale", type=int, default=2, help="CPU sample = 1 frame at H/s x W/s")
     ap.add_argument("--bucket-mb", type=float, default=16.0)
@@ -71,7 +92,10 @@ def parse():
     ap.add_argument("--f32-train-warmup", type=int, default=3)
     ap.add_argument("--ns-batch", type=int, default=32,
                     help="north-star leg: fp32 1080p inference (conv2d forward) at this batch per GPU; 0 = skip")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------- kernel timing
@@ -441,8 +465,21 @@ def _print_detail(det, steps, tag):
               file=sys.stderr)
 
 
-def main():
-    args = parse()
+def dump_outputs(path, arrays):
+    """Write each device tensor as float32 path/<name>.npy; one of more than DUMP_SAMPLE
+    elements is reduced to DUMP_SAMPLE of them at fixed (seeded, sorted) flat indices."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach()
+        if a.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.numel(), size=DUMP_SAMPLE))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
+
+
+def main(argv=None):
+    args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(args))
     import torch
@@ -460,7 +497,7 @@ def main():
     with contextlib.redirect_stdout(io.StringIO()):
         model = C.U_net(input_size=(args.height, args.width, 3), pad=True, dtype=args.dtype, seed=0,
                         verbose=False)
-    P_init = model.named_weights() if rank == 0 else None
+    P_init = model.named_weights() if rank == 0 and args.full else None  # the CPU baseline's weights
     eng = model._engine()
     dp = None
     if world > 1:
@@ -470,7 +507,7 @@ def main():
         if rank == 0:
             print(f"[bench] process group: backend={torch.distributed.get_backend()} world_size={pg_world}, "
                   f"{len(dp.buckets)} gradient buckets", file=sys.stderr)
-    timer = KernelTimer(ops, torch)
+    timer = KernelTimer(ops, torch) if args.full else None  # wraps the ops' entry points: --full only
 
     g = torch.Generator(device="cuda")
     g.manual_seed(1234 + 7919 * rank)
@@ -483,7 +520,7 @@ def main():
         if args.mode == "infer":
             yhat = torch.empty(B, args.height, args.width, 3, device="cuda", dtype=torch.float32)
             eng.predict_into(x, yhat)  # Model.predict's path (fused head included)
-            return None
+            return yhat
         kw = dict(seed=i * world + rank, lr=opt.lr, rho=opt.rho, eps=opt.epsilon)
         if dp is not None:
             kw.update(sync=dp.finish, grad_scale=dp.grad_scale)
@@ -497,7 +534,9 @@ def main():
     def timed(n, first):
         barrier()
         t0 = time.perf_counter()
-        out = [step(first + i) for i in range(n)]
+        out = None
+        for i in range(n):
+            out = step(first + i)  # the last step's result: what --dump-outputs writes
         barrier()
         el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
         if world > 1:
@@ -507,9 +546,28 @@ def main():
     for i in range(args.warmup):
         step(i)
     # pass 1: throughput (no per-launch instrumentation inside the timed region)
-    elapsed, losses = timed(args.steps, args.warmup)
+    elapsed, last = timed(args.steps, args.warmup)
     frames = B * world * args.steps
     fps = frames / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"yhat": last} if args.mode == "infer" else
+                     {"loss_acc": last, "params": eng.params, "bufs": eng.bufs})
+    res = "1080p" if (args.height, args.width) == (1080, 1920) else f"{args.width}x{args.height}"
+    metric = f"{res} SDR->HDR frames/sec (fwd+bwd)" if args.mode == "train" else f"{res} SDR->HDR frames/sec (fwd)"
+    line = {"metric": metric, "value": round(fps, 3), "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16" if args.dtype == "bfloat16" else "f32", "data": "synthetic",
+            "config": {"workload": f"U-Net (model.py:204) {args.mode} step, {args.width}x{args.height} "
+                                   f"frames padded to {W}x{H}, {B} frames/GPU",
+                       "global_batch": B * world, "frame": [args.height, args.width],
+                       "padded": [H, W], "parallelism": f"dp{world}"}}
+    if not args.full:  # a plain run ends here
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     # pass 2: the same steps with every conv launch bracketed by HIP events (roofline),
     # and the all-reduce wait left exposed on the compute stream after overlap
     timer.reset()
@@ -534,8 +592,8 @@ def main():
     if rank == 0:
         _print_agg(agg, args.mode)
         _print_detail(timer.detail(), k2, args.mode)
-        if losses and losses[-1] is not None:
-            print(f"[bench] last loss/acc: {losses[-1].cpu().numpy().tolist()}", file=sys.stderr)
+        if args.mode == "train":
+            print(f"[bench] last loss/acc: {last.cpu().numpy().tolist()}", file=sys.stderr)
         print(f"[bench] peak mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB, "
               f"step {elapsed / args.steps * 1e3:.1f} ms (instrumented pass {elapsed2 / k2 * 1e3:.1f} ms)"
               + (f", exposed all-reduce {exposed['ms_per_step']} ms/step" if exposed else ""), file=sys.stderr)
@@ -596,7 +654,7 @@ def main():
     infer = ns = k4 = f32t = None
     if args.mode == "train" and (args.infer_batch > 0 or args.k4_batch > 0 or args.ns_batch > 0
                                  or args.f32_train_batch > 0):
-        del eng, model, x, t, losses
+        del eng, model, x, t, last
         timer.rec = []
         C.clear_session()
         torch.cuda.empty_cache()
@@ -613,18 +671,8 @@ def main():
         f32t = guarded(f32_train_leg, args, rank, world, timer, barrier, agree, cpu)
 
     if rank == 0:
-        res = "1080p" if (args.height, args.width) == (1080, 1920) else f"{args.width}x{args.height}"
-        metric = f"{res} SDR->HDR frames/sec (fwd+bwd)" if args.mode == "train" else f"{res} SDR->HDR frames/sec (fwd)"
-        line = {"metric": metric, "value": round(fps, 3), "unit": "frames/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "bf16" if args.dtype == "bfloat16" else "f32", "data": "synthetic",
-                "config": {"workload": f"U-Net (model.py:204) {args.mode} step, {args.width}x{args.height} "
-                                       f"frames padded to {W}x{H}, {B} frames/GPU",
-                           "global_batch": B * world, "frame": [args.height, args.width],
-                           "padded": [H, W], "parallelism": f"dp{world}",
-                           "gflop_per_frame": round(step_flops / B / 1e9, 1)},
-                "roofline": roof, "cpu_baseline": cpu}
+        line["config"]["gflop_per_frame"] = round(step_flops / B / 1e9, 1)
+        line.update(roofline=roof, cpu_baseline=cpu)
         if exposed is not None:
             line["allreduce_exposed"] = exposed
         if replicas is not None:

@@ -6,7 +6,7 @@ during backward.
   (``Model.fit_generator(..., distributed=True)`` over rank-sharded, zip-paired
   ImageDataGenerator streams): every rank must end with bit-identical parameters
   and moving statistics equal to a single-process replay at the global batch.
-* ``bench.py --gpus 2`` must start its two ranks by itself (no torchrun
+* ``bench.py --gpus 2 --full`` must start its two ranks by itself (no torchrun
   environment), report ``n_gpus == 2`` / ``dp2`` and identical replicas.
 
 RCCL refuses two ranks on one GPU, so on this box the RCCL path runs as a one-rank
@@ -49,7 +49,7 @@ def test_bench_spawns_ranks():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--height", "64", "--width", "96",
-           "--batch", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--infer-batch", "1", "--bucket-mb", "0.5", "--k4-batch", "1", "--k4-steps", "1",
+           "--batch", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--infer-batch", "1", "--bucket-mb", "0.5", "--k4-batch", "1", "--k4-steps", "1",
            "--f32-train-batch", "1", "--f32-train-steps", "1",
            "--ns-batch", "2"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=240, cwd=ROOT)

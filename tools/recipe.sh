@@ -4,7 +4,8 @@
 #
 #   bash tools/recipe.sh suite    <tag>                        full `pytest -m gpu`
 #   bash tools/recipe.sh tests    <tag> [LIB=<.so>] <pytest args...>   a subset (optionally on a variant library)
-#   bash tools/recipe.sh bench    <tag> [bench args...]        bench.py line -> <tag>_bench.json (+ .err)
+#   bash tools/recipe.sh bench    <tag> [bench args...]        bench.py line -> <tag>_bench.json (+ .err);
+#                                                              --full adds the roofline, CPU and secondary legs
 #   bash tools/recipe.sh evidence <tag>                        PMC traffic per shape, rocprofv3 stats of the
 #                                                              1080p and 4K training legs, default bench line
 #   bash tools/recipe.sh layers   <tag> <layers> <ops> <lib.so>...   per-layer A/B: in-tree library vs variants,
@@ -55,7 +56,7 @@ evidence)
   bash "$R/tools/profile_round.sh" "${tag}_4k" --height 2160 --width 3840 --batch 8 --steps 5 --warmup 2 \
     --infer-batch 0 --ns-batch 0 --k4-batch 0 --f32-train-batch 0
   cd "$R"
-  $T 900 python3 bench.py > "$O/${tag}_bench.json" 2> "$O/${tag}_bench.err"
+  $T 900 python3 bench.py --full > "$O/${tag}_bench.json" 2> "$O/${tag}_bench.err"
   cat "$O/${tag}_bench.json" ;;
 layers)
   L=$1; P=$2; shift 2
@@ -75,7 +76,7 @@ benchab)
   for e in "" "$sw" "" "$sw"; do
     case $e in *.so) envs="CNNITMO_LIB=$e" ;; "") envs="CNNITMO_LIB=${BASE:-$LIB}" ;; *) envs=$e ;; esac
     echo "== ${e:-baseline}"
-    env $envs $T 600 python3 bench.py --no-cpu "$@" 2>> "$O/${tag}_ab.err" | grep -E '^\{' | python3 -c \
+    env $envs $T 600 python3 bench.py --full --no-cpu "$@" 2>> "$O/${tag}_ab.err" | grep -E '^\{' | python3 -c \
       "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], r['kernel'], r['achieved'])"
   done > "$O/${tag}_ab.txt"
   cat "$O/${tag}_ab.txt" ;;
@@ -106,7 +107,7 @@ benchattrib)
              "SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_WAVES GRBM_GUI_ACTIVE" \
              "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM SQ_LDS_UNALIGNED_STALL SQ_INST_CYCLES_VMEM_WR GRBM_GUI_ACTIVE"; do
     CNNITMO_LIB=$lib timeout -s KILL 240 rocprofv3 --pmc $ctr --output-format csv -d "$A/p$i" -o run -- \
-      python3 "$R/bench.py" --no-cpu --steps 1 --warmup 1 --infer-batch 0 --ns-batch 0 --k4-batch 0 \
+      python3 "$R/bench.py" --full --no-cpu --steps 1 --warmup 1 --infer-batch 0 --ns-batch 0 --k4-batch 0 \
       --f32-train-batch 0 "$@" > "$A/p$i.log" 2>&1
     i=$((i+1))
   done
@@ -114,7 +115,7 @@ benchattrib)
 mfma)
   cd /tmp && export TMPDIR=/tmp
   timeout -s KILL 240 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE \
-    --output-format csv -d "$O/mfma_$tag" -o run -- python3 "$R/bench.py" --no-cpu --steps 1 --warmup 1 \
+    --output-format csv -d "$O/mfma_$tag" -o run -- python3 "$R/bench.py" --full --no-cpu --steps 1 --warmup 1 \
     --infer-batch 0 --ns-batch 0 --k4-batch 0 --f32-train-batch 0 "$@" > "$O/mfma_${tag}.log" 2>&1 ;;
 *)
   echo "unknown recipe step: $cmd" >&2; exit 2 ;;
