@@ -9,8 +9,9 @@ from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2D
 from .model import Model, RMSprop, load_model
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import CSVLogger, LambdaCallback, ModelCheckpoint
+from . import metrics
 
 __all__ = ["Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
            "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
-           "LambdaCallback", "ModelCheckpoint"]
+           "LambdaCallback", "ModelCheckpoint", "metrics"]

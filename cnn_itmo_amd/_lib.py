@@ -41,6 +41,8 @@ SIGNATURES = {
     "cnnitmo_tonemap_stats": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
     "cnnitmo_tonemap_apply": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
     "cnnitmo_inverse_reinhard_apply": (i32, [i32, vp, i32, i32, i32, vp, vp, f64, f64, vp, vp]),
+    "cnnitmo_image_metrics_workspace_bytes": (i64, [i32, i32, i32]),
+    "cnnitmo_image_metrics": (i32, [i32, vp, vp, i32, i32, i32, f64, vp, vp, i64, vp]),
     "cnnitmo_conv3x3_fwd": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "cnnitmo_conv3x3_fwd_cat": (i32, [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32,
                                       i32, i32, vp, vp, vp, vp, vp]),

@@ -3,7 +3,9 @@
 from __future__ import annotations
 
 import csv
+import math
 import os
+import warnings
 
 
 class Callback:
@@ -61,15 +63,40 @@ class CSVLogger(Callback):
 
 
 class ModelCheckpoint(Callback):
-    """ModelCheckpoint(filepath) -- main.py:123-124; filepath may use {epoch} and log keys."""
+    """ModelCheckpoint(filepath) -- main.py:123-124; filepath may use {epoch} and log keys.
+
+    ``save_best_only=True`` saves only when the ``monitor`` log improves on the best so far:
+    ``mode`` 'min' / 'max', or 'auto' = max when the monitored name contains 'acc', 'psnr'
+    or 'ssim' and min otherwise.  A monitored key missing from the logs skips the save with
+    a warning.  The default saves every ``period`` epochs."""
 
     def __init__(self, filepath, monitor="val_loss", verbose=0, save_best_only=False, mode="auto",
                  save_weights_only=False, period=1):
         self.filepath, self.verbose, self.weights_only, self.period = filepath, verbose, save_weights_only, period
+        if mode not in ("auto", "min", "max"):
+            warnings.warn(f"ModelCheckpoint mode {mode!r} is unknown, fallback to auto mode.", RuntimeWarning)
+            mode = "auto"
+        if mode == "auto":
+            mode = "max" if any(s in monitor for s in ("acc", "psnr", "ssim")) else "min"
+        self.monitor, self.save_best_only, self.mode = monitor, bool(save_best_only), mode
+        self.best = -math.inf if mode == "max" else math.inf
+
+    def _improved(self, value):
+        return value > self.best if self.mode == "max" else value < self.best
 
     def on_epoch_end(self, epoch, logs=None):
         if (epoch + 1) % self.period:
             return
+        if self.save_best_only:
+            value = (logs or {}).get(self.monitor)
+            if value is None:
+                warnings.warn(f"Can save best model only with {self.monitor} available, skipping.", RuntimeWarning)
+                return
+            if not self._improved(value):
+                if self.verbose:
+                    print(f"Epoch {epoch + 1}: {self.monitor} did not improve from {self.best:.5f}")
+                return
+            self.best = value
         path = self.filepath.format(epoch=epoch + 1, **(logs or {}))
         (self.model.save_weights if self.weights_only else self.model.save)(path)
         if self.verbose:

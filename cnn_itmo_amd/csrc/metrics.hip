@@ -1,0 +1,340 @@
+// Image-fidelity metrics of two NHWC RGB fp32 batches, per image (cnnitmo_image_metrics):
+//
+//   mse   = mean over h*w*3 of (a-b)^2, psnr = 10*log10(max_val^2/mse)      (tf.image.psnr)
+//   ssim  = mean over the valid window positions and the 3 channels of
+//           ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2))
+//           with an 11x11 Gaussian window (sigma 1.5), biased weighted moments,
+//           C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2   (tf.image.ssim, Wang et al. 2004)
+//
+// One pass over both images; no filtered map or SSIM map goes to global memory.  A row
+// of an NHWC RGB image is 3*w contiguous floats and the horizontal taps of one channel are
+// 3 floats apart, so the kernel works on "float columns": the SSIM map of an image is
+// (h-10) rows x 3*(w-10) columns, column j reading input columns j + 3k, k = 0..10.
+//
+// ssim_mse_kernel: one workgroup owns TR x TC positions of that map.  It stages the
+// (TR+10) x (TC+30) input window of both images through LDS (16-byte loads where the row
+// pitch allows them), accumulating (a-b)^2 of the elements it owns on the way (its own
+// TR x TC corner; the last tile row / column also own the 10-row / 30-column apron, so
+// every element is counted once).  Then the separable filter of the five maps x, y, x^2,
+// y^2, xy: the horizontal pass leaves fp64 row sums in LDS (each thread 4 outputs that
+// share taps: 14 reads of each image for 4 x 11 taps), the vertical pass reads them back
+// (each thread 4 rows of one column: 14 x 5 reads), forms the SSIM term and sums it.
+//
+// Numerics: everything after the load is fp64.  The products x^2, y^2, xy of fp32 values
+// are exact in fp64, so sx^2 = E[x^2] - mx^2 cancels against C2 = 9e-4 with ~1e-16 of
+// error instead of fp32's 1e-7 (which moves SSIM of flat images by 1e-4).  The filter taps
+// accumulate with explicit fma(); every other expression is compiled under
+// `#pragma clang fp contract(off)`.
+//
+// Reduction: in-wave shuffles, then LDS across the waves, one (ssim sum, squared-error sum)
+// pair per workgroup into the caller's workspace; metrics_final_kernel folds an image's
+// pairs in a fixed order in fp64.  No atomics: two runs are bitwise equal.
+//
+// what == 1 (MSE/PSNR only, any h, w >= 1) takes mse_kernel, a plain strided reduction
+// with the same two-level fold.
+#include <math.h>
+
+#include <algorithm>
+
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int NT = 256;                  // threads per workgroup
+constexpr int TR = 16;                   // map rows per tile
+constexpr int TC = 48;                   // map float-columns per tile (16 pixels)
+constexpr int R = 5;                     // window radius: 11 taps
+constexpr int NTAP = 2 * R + 1;
+constexpr int IR = TR + 2 * R;           // staged input rows: 26
+constexpr int IC = TC + 3 * 2 * R;       // staged input float-columns: 78
+constexpr int ICP = 80;                  // padded to whole 16-byte chunks
+constexpr int G = 4;                     // outputs per thread in either pass
+constexpr int GW = G + 2 * R;            // inputs those outputs share: 14
+constexpr int MSE_BLK = 128;             // workgroups per image of mse_kernel
+static_assert(TC % (3 * G) == 0 && TR % G == 0 && ICP % 4 == 0 && ICP >= IC && TC % 4 == 0, "tile");
+
+struct Taps {
+  double g[NTAP];
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum of (v0, v1) over the workgroup -> thread 0
+__device__ __forceinline__ void block_sum2(double& v0, double& v1, double (*sh)[2]) {
+  v0 = wave_sum_f64(v0);
+  v1 = wave_sum_f64(v1);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+    sh[wave][0] = v0;
+    sh[wave][1] = v1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v0 = sh[0][0];
+    v1 = sh[0][1];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
+      v0 += sh[i][0];
+      v1 += sh[i][1];
+    }
+  }
+}
+
+// part [n][nblk][2] = (ssim sum, squared-error sum) of a tile; grid (tiles_x, tiles_y, n)
+template <bool VEC>
+__global__ __launch_bounds__(NT) void ssim_mse_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                      int h, int w, Taps tp, double c1, double c2,
+                                                      double* __restrict__ part) {
+  __shared__ float sa[IR][ICP];
+  __shared__ float sb[IR][ICP];
+  __shared__ double hs[5][IR][TC];
+  __shared__ double red[NT / 64][2];
+
+  const int tid = threadIdx.x;
+  const int w3 = 3 * w;
+  const int mh = h - 2 * R, mw3 = 3 * (w - 2 * R);  // the map's size
+  const int r0 = blockIdx.y * TR, c0 = blockIdx.x * TC;
+  const long img = (long)blockIdx.z * h * w3;
+  // rows / columns of the staged window whose squared error this tile counts
+  const int own_r = blockIdx.y == gridDim.y - 1 ? IR : TR;
+  const int own_c = blockIdx.x == gridDim.x - 1 ? ICP : TC;
+
+  double sq = 0.0;
+  if (VEC) {  // w3 % 4 == 0 and 16-byte aligned bases: a chunk is inside the row or outside it
+    for (int i = tid; i < IR * (ICP / 4); i += NT) {
+      const int r = i / (ICP / 4), c = (i % (ICP / 4)) * 4;
+      const int gr = r0 + r, gc = c0 + c;
+      float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
+      if (gr < h && gc < w3) {
+        const long o = img + (long)gr * w3 + gc;
+        va = *reinterpret_cast<const float4*>(a + o);
+        vb = *reinterpret_cast<const float4*>(b + o);
+        if (r < own_r && c < own_c) {
+          const double d0 = (double)va.x - (double)vb.x, d1 = (double)va.y - (double)vb.y;
+          const double d2 = (double)va.z - (double)vb.z, d3 = (double)va.w - (double)vb.w;
+          sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+      }
+      *reinterpret_cast<float4*>(&sa[r][c]) = va;
+      *reinterpret_cast<float4*>(&sb[r][c]) = vb;
+    }
+  } else {
+    for (int i = tid; i < IR * ICP; i += NT) {
+      const int r = i / ICP, c = i % ICP;
+      const int gr = r0 + r, gc = c0 + c;
+      float va = 0.f, vb = 0.f;
+      if (gr < h && gc < w3) {
+        const long o = img + (long)gr * w3 + gc;
+        va = a[o];
+        vb = b[o];
+        if (r < own_r && c < own_c) {
+          const double d = (double)va - (double)vb;
+          sq += d * d;
+        }
+      }
+      sa[r][c] = va;
+      sb[r][c] = vb;
+    }
+  }
+  __syncthreads();
+
+  // horizontal pass: thread = (row, base column cb); outputs cb + 3t, t < G, from inputs cb + 3m, m < GW
+  for (int i = tid; i < IR * (TC / G); i += NT) {
+    const int r = i / (TC / G), gi = i % (TC / G);
+    const int cb = (gi / 3) * (3 * G) + gi % 3;
+    double acc[5][G];
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+      for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
+#pragma unroll
+    for (int m = 0; m < GW; ++m) {
+      const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
+      const double xx = x * x, yy = y * y, xy = x * y;
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        if (m - t >= 0 && m - t < NTAP) {
+          const double g = tp.g[m - t];
+          acc[0][t] = fma(g, x, acc[0][t]);
+          acc[1][t] = fma(g, y, acc[1][t]);
+          acc[2][t] = fma(g, xx, acc[2][t]);
+          acc[3][t] = fma(g, yy, acc[3][t]);
+          acc[4][t] = fma(g, xy, acc[4][t]);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+      for (int t = 0; t < G; ++t) hs[k][r][cb + 3 * t] = acc[k][t];
+  }
+  __syncthreads();
+
+  // vertical pass: thread = (row group, column); outputs rows 4*rg + t from row sums 4*rg + m
+  double ss = 0.0;
+  for (int i = tid; i < (TR / G) * TC; i += NT) {
+    const int rb = (i / TC) * G, c = i % TC;
+    if (r0 + rb >= mh || c0 + c >= mw3) continue;
+    double acc[5][G];
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+      for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
+#pragma unroll
+    for (int m = 0; m < GW; ++m) {
+      double v[5];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) v[k] = hs[k][rb + m][c];
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        if (m - t >= 0 && m - t < NTAP) {
+          const double g = tp.g[m - t];
+#pragma unroll
+          for (int k = 0; k < 5; ++k) acc[k][t] = fma(g, v[k], acc[k][t]);
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < G; ++t) {
+      if (r0 + rb + t < mh) {
+        const double mx = acc[0][t], my = acc[1][t];
+        const double mxx = mx * mx, myy = my * my, mxy = mx * my;
+        const double vx = acc[2][t] - mxx, vy = acc[3][t] - myy, cxy = acc[4][t] - mxy;
+        const double num = (2.0 * mxy + c1) * (2.0 * cxy + c2);
+        const double den = (mxx + myy + c1) * (vx + vy + c2);
+        ss += num / den;
+      }
+    }
+  }
+
+  block_sum2(ss, sq, red);
+  if (tid == 0) {
+    const long nblk = (long)gridDim.x * gridDim.y;
+    double* d = part + ((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+    d[0] = ss;
+    d[1] = sq;
+  }
+}
+
+// part [n][MSE_BLK][2] = (0, squared-error sum); len = h*w*3 elements per image; grid (MSE_BLK, n)
+template <bool VEC>
+__global__ __launch_bounds__(NT) void mse_kernel(const float* __restrict__ a, const float* __restrict__ b, long len,
+                                                 double* __restrict__ part) {
+  __shared__ double red[NT / 64][2];
+  const long img = (long)blockIdx.y * len;
+  double sq = 0.0, zero = 0.0;
+  if (VEC) {  // len % 4 == 0 and 16-byte aligned bases
+    for (long i = ((long)blockIdx.x * NT + threadIdx.x) * 4; i < len; i += (long)MSE_BLK * NT * 4) {
+      const float4 va = *reinterpret_cast<const float4*>(a + img + i);
+      const float4 vb = *reinterpret_cast<const float4*>(b + img + i);
+      const double d0 = (double)va.x - (double)vb.x, d1 = (double)va.y - (double)vb.y;
+      const double d2 = (double)va.z - (double)vb.z, d3 = (double)va.w - (double)vb.w;
+      sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+  } else {
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < len; i += (long)MSE_BLK * NT) {
+      const double d = (double)a[img + i] - (double)b[img + i];
+      sq += d * d;
+    }
+  }
+  block_sum2(zero, sq, red);
+  if (threadIdx.x == 0) {
+    double* d = part + ((long)blockIdx.y * MSE_BLK + blockIdx.x) * 2;
+    d[0] = 0.0;
+    d[1] = sq;
+  }
+}
+
+// one workgroup per image: thread t folds pairs t, t + NT, ... in order, then a fixed tree
+__global__ __launch_bounds__(NT) void metrics_final_kernel(const double* __restrict__ part, long nblk, int what,
+                                                           double n_elem, double n_pos, double max_val,
+                                                           double* __restrict__ out) {
+  __shared__ double sh[2][NT];
+  const int im = blockIdx.x;
+  double ss = 0.0, sq = 0.0;
+  for (long i = threadIdx.x; i < nblk; i += NT) {
+    ss += part[((long)im * nblk + i) * 2];
+    sq += part[((long)im * nblk + i) * 2 + 1];
+  }
+  sh[0][threadIdx.x] = ss;
+  sh[1][threadIdx.x] = sq;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (what & 1) {
+      const double mse = sh[1][0] / n_elem;
+      out[3 * im] = mse;
+      out[3 * im + 1] = 10.0 * log10(max_val * max_val / mse);  // mse == 0: +inf
+    }
+    if (what & 2) out[3 * im + 2] = sh[0][0] / n_pos;
+  }
+}
+
+long tiles_of(int h, int w) {
+  if (h < NTAP || w < NTAP) return 0;
+  const long ty = (h - 2 * R + TR - 1) / TR, tx = (3L * (w - 2 * R) + TC - 1) / TC;
+  return ty * tx;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" long cnnitmo_image_metrics_workspace_bytes(int n, int h, int w) {
+  if (n <= 0 || h <= 0 || w <= 0) return 0;
+  return (long)n * std::max<long>(tiles_of(h, w), MSE_BLK) * 2 * (long)sizeof(double);
+}
+
+extern "C" int cnnitmo_image_metrics(int what, const float* a, const float* b, int n, int h, int w, double max_val,
+                                     double* out, void* workspace, long workspace_bytes, void* stream) {
+  CNN_REQUIRE(what >= 1 && what <= 3, "image_metrics: what %d (bit 0 = MSE/PSNR, bit 1 = SSIM)", what);
+  CNN_REQUIRE(a && b && out && workspace, "image_metrics: null pointer");
+  CNN_REQUIRE(n > 0 && n <= 65535 && h > 0 && w > 0, "image_metrics: bad shape n=%d h=%d w=%d", n, h, w);
+  CNN_REQUIRE(3L * w < (1L << 30) && h <= 65535 * TR, "image_metrics: image %d x %d too large", h, w);
+  CNN_REQUIRE(max_val > 0.0, "image_metrics: max_val %g", max_val);
+  CNN_REQUIRE(!(what & 2) || (h >= NTAP && w >= NTAP), "image_metrics: SSIM needs h, w >= %d, got %d x %d", NTAP, h,
+              w);
+  CNN_REQUIRE(workspace_bytes >= cnnitmo_image_metrics_workspace_bytes(n, h, w),
+              "image_metrics: workspace too small (%ld < %ld bytes)", workspace_bytes,
+              cnnitmo_image_metrics_workspace_bytes(n, h, w));
+  hipStream_t s = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  const double n_elem = (double)h * w * 3.0;
+  long nblk;
+  double n_pos = 1.0;
+  if (what & 2) {
+    Taps tp;
+    double sum = 0.0;
+    for (int i = 0; i < NTAP; ++i) sum += tp.g[i] = exp(-(double)((i - R) * (i - R)) / 4.5);
+    for (int i = 0; i < NTAP; ++i) tp.g[i] /= sum;
+    const double c1 = (0.01 * max_val) * (0.01 * max_val), c2 = (0.03 * max_val) * (0.03 * max_val);
+    const dim3 grid((unsigned)((3L * (w - 2 * R) + TC - 1) / TC), (unsigned)((h - 2 * R + TR - 1) / TR), n);
+    nblk = (long)grid.x * grid.y;
+    n_pos = (double)(h - 2 * R) * (w - 2 * R) * 3.0;
+    if ((3L * w) % 4 == 0 && aligned16(a) && aligned16(b))
+      hipLaunchKernelGGL(ssim_mse_kernel<true>, grid, dim3(NT), 0, s, a, b, h, w, tp, c1, c2, part);
+    else
+      hipLaunchKernelGGL(ssim_mse_kernel<false>, grid, dim3(NT), 0, s, a, b, h, w, tp, c1, c2, part);
+  } else {
+    const long len = (long)h * w * 3;
+    nblk = MSE_BLK;
+    if (len % 4 == 0 && aligned16(a) && aligned16(b))
+      hipLaunchKernelGGL(mse_kernel<true>, dim3(MSE_BLK, n), dim3(NT), 0, s, a, b, len, part);
+    else
+      hipLaunchKernelGGL(mse_kernel<false>, dim3(MSE_BLK, n), dim3(NT), 0, s, a, b, len, part);
+  }
+  hipLaunchKernelGGL(metrics_final_kernel, dim3(n), dim3(NT), 0, s, (const double*)part, nblk, what, n_elem, n_pos,
+                     max_val, out);
+  return cnnitmo_check_launch("image_metrics");
+}

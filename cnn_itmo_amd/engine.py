@@ -1119,11 +1119,38 @@ class Engine:
         self.step += 1
         return loss_acc
 
-    def evaluate_batch(self, x, target):
+    def evaluate_batch(self, x, target, image_metrics=()):
+        """Device tensor [loss, acc] of the batch.  image_metrics (names out of 'psnr', 'ssim'):
+        returns (loss_acc, per_image) with per_image a float64 [n, len(image_metrics)] device
+        tensor of the prediction against the target's valid rows (cnnitmo_image_metrics).  The
+        loss path is the same calls either way; the prediction is then written the way predict()
+        writes it (the head in its producer's epilogue where fused, the head kernel otherwise)
+        from the activations this forward left."""
         n = self.forward(x, training=False)
         loss_acc = torch.empty(2, device=self.device, dtype=torch.float32)
         saved = self.grads.clone()
-        self.stages[-1].loss_and_grad(n, target.contiguous().float(), loss_acc)
+        target = target.contiguous().float()
+        self.stages[-1].loss_and_grad(n, target, loss_acc)
         self.grads.copy_(saved)
+        if not image_metrics:
+            self._release()
+            return loss_acc
+        cols = {"psnr": 1, "ssim": 2}
+        if any(k not in cols for k in image_metrics):
+            raise ValueError(f"image_metrics {image_metrics!r}: names out of {sorted(cols)}")
+        head = self.stages[-1]
+        yhat = torch.empty(n, self.h_valid, self.model.inputs[0].shape[1], 3, device=self.device,
+                           dtype=torch.float32)
+        if tuple(target.shape) != tuple(yhat.shape):
+            raise ValueError(f"image metrics: target of shape {tuple(target.shape)}, prediction {tuple(yhat.shape)}")
+        if head.fused:
+            self._yhat = yhat
+            try:
+                head.vin.producer.forward(n, False)
+            finally:
+                self._yhat = None
+        head.infer(n, yhat)
         self._release()
-        return loss_acc
+        what = (ops.MSE_PSNR if "psnr" in image_metrics else 0) | (ops.SSIM if "ssim" in image_metrics else 0)
+        out = ops.image_metrics(what, yhat, target, 1.0)
+        return loss_acc, out[:, [cols[k] for k in image_metrics]]

@@ -118,10 +118,13 @@ def model_config(model):
 
 
 def training_config(model):
+    from .model import _METRIC_CONFIG
     o = model.optimizer
+    # the compiled metrics in order ('accuracy', 'psnr', 'ssim'); load_model compiles with them
+    metrics = [_METRIC_CONFIG[k] for k in getattr(model, "metrics_names", [])[1:]]
     return {"optimizer_config": {"class_name": "RMSprop",
                                  "config": {"lr": o.lr, "rho": o.rho, "decay": 0.0, "epsilon": o.epsilon}},
-            "loss": "mse", "metrics": ["accuracy"] if len(getattr(model, "metrics_names", [])) > 1 else [],
+            "loss": "mse", "metrics": metrics,
             "sample_weight_mode": None, "loss_weights": None}
 
 

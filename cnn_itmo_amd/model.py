@@ -40,6 +40,23 @@ class RMSprop:
             raise NotImplementedError("RMSprop decay is not on the path")
 
 
+_METRIC_KEYS = {"accuracy": "acc", "acc": "acc", "categorical_accuracy": "acc", "psnr": "psnr", "ssim": "ssim"}
+_METRIC_CONFIG = {"acc": "accuracy", "psnr": "psnr", "ssim": "ssim"}  # the names training_config writes
+
+
+def _metric_key(m):
+    """compile()'s metric -> its metrics_names / log key: 'accuracy' (Keras' categorical
+    accuracy of the 3 channels, shown as 'acc'), 'psnr', 'ssim' or metrics.psnr / metrics.ssim."""
+    if callable(m):
+        from . import metrics as M
+        for k, f in (("psnr", M.psnr), ("ssim", M.ssim)):
+            if m is f:
+                return k
+    elif isinstance(m, str) and m in _METRIC_KEYS:
+        return _METRIC_KEYS[m]
+    raise NotImplementedError(f"metric {m!r}")
+
+
 def _to_internal(layer, wname, arr):
     """Keras layout -> engine layout (Conv2D kernel HWIO -> OHWI)."""
     if isinstance(layer, Conv2D) and wname == "kernel":
@@ -148,11 +165,15 @@ class Model:
             optimizer = RMSprop()
         if loss not in ("mse", "mean_squared_error"):
             raise NotImplementedError(f"loss {loss!r} (only 'mse' is on the path)")
+        names = []
         for m in metrics or []:
-            if m not in ("accuracy", "acc", "categorical_accuracy"):
-                raise NotImplementedError(f"metric {m!r}")
+            k = _metric_key(m)
+            if k not in names:
+                names.append(k)
         self.optimizer = optimizer
-        self.metrics_names = ["loss"] + (["acc"] if metrics else [])
+        self.metrics_names = ["loss"] + names
+        # 'psnr' / 'ssim' in the order given: computed by evaluate() and for the validation logs
+        self.image_metrics = [k for k in names if k != "acc"]
         if dtype is not None:
             self.set_dtype(dtype)
 
@@ -276,24 +297,57 @@ class Model:
         la = eng.train_step(self._to_dev(x), self._to_dev(y), lr=o.lr, rho=o.rho, eps=o.epsilon, **kw)
         return la.cpu().numpy().tolist() if sync else la
 
-    def evaluate(self, x, y, batch_size=32, verbose=0):
+    def _evaluate_means(self, x, y, batch_size):
+        """Sample means of loss, acc and the compiled image metrics: ({key: mean}, frames)."""
         self._check_compiled()
         eng = self._engine()
-        tot, n = np.zeros(2), 0
+        im = list(getattr(self, "image_metrics", []))
+        tot, imtot, n = np.zeros(2), np.zeros(len(im)), 0
         for i in range(0, len(x), batch_size):
             xb, yb = x[i:i + batch_size], y[i:i + batch_size]
-            la = eng.evaluate_batch(self._to_dev(xb), self._to_dev(yb)).cpu().numpy()
-            tot += la * len(xb)
+            if im:
+                la, per_image = eng.evaluate_batch(self._to_dev(xb), self._to_dev(yb), image_metrics=im)
+                for row in per_image.cpu().numpy():  # in frame order, whatever else is computed
+                    imtot += row
+            else:
+                la = eng.evaluate_batch(self._to_dev(xb), self._to_dev(yb))
+            tot += la.cpu().numpy() * len(xb)
             n += len(xb)
-        return (tot / n).tolist()
+        means = dict(zip(["loss", "acc"] + im, (tot / n).tolist() + (imtot / n).tolist()))
+        return means, n
+
+    def evaluate(self, x, y, batch_size=32, verbose=0):
+        """[loss, acc]; compiled with 'psnr' / 'ssim', the values of ``metrics_names`` in
+        that order (image metrics are means of the per-image values, prediction against
+        the target's valid rows; loss and acc are the same numbers either way)."""
+        means, _ = self._evaluate_means(x, y, batch_size)
+        if not getattr(self, "image_metrics", []):
+            return [means["loss"], means["acc"]]
+        return [means[k] for k in self.metrics_names]
+
+    def _validation_logs(self, validation_data, validation_steps=None):
+        """val_loss, val_acc and val_<image metric> of an epoch: sample-weighted means over
+        the validation batches, summed over the DP ranks before dividing (every rank's
+        frames weigh the same, however unequal the shares)."""
+        keys = ["loss", "acc"] + list(getattr(self, "image_metrics", []))
+        vt = np.zeros(len(keys) + 1)
+        for _ in range(validation_steps or 1):
+            xv, yv = next(validation_data) if hasattr(validation_data, "__next__") else validation_data
+            means, nv = self._evaluate_means(xv, yv, batch_size=len(xv))
+            vt[:-1] += np.asarray([means[k] for k in keys]) * nv
+            vt[-1] += nv
+        vt = self._allreduce_sum(vt)
+        return {"val_" + k: vt[i] / vt[-1] for i, k in enumerate(keys)}
 
     def fit(self, x, y, batch_size=32, epochs=1, verbose=1, callbacks=None, shuffle=True, distributed=None,
-            **kw):
+            validation_data=None, **kw):
         """keras Model.fit.  The permutation is drawn from numpy's global RNG each epoch
         (as Keras does).  Distributed, ``batch_size`` is PER RANK, as for the generators
         (ImageDataGenerator.flow / flow_from_directory): every rank walks rank 0's
         permutation in global batches of batch_size * world frames and trains on its
-        contiguous share; a global batch with fewer frames than ranks is dropped."""
+        contiguous share; a global batch with fewer frames than ranks is dropped.
+        ``validation_data`` (x, y): evaluated in one batch after every epoch (this rank's
+        share when distributed, as in fit_generator)."""
         if distributed or (distributed is None and self._dp is None and _dist_world() > 1):
             self.distribute()
         r, w = self.world
@@ -333,7 +387,7 @@ class Model:
         it = batches()
         steps = sum(1 for i in range(0, len(x), gb) if len(x) - i >= w)
         return self.fit_generator(g, steps_per_epoch=steps, epochs=epochs, verbose=verbose,
-                                  callbacks=callbacks)
+                                  callbacks=callbacks, validation_data=validation_data)
 
     def fit_generator(self, generator, steps_per_epoch=None, epochs=1, verbose=1, callbacks=None,
                       validation_data=None, validation_steps=None, initial_epoch=0, distributed=None,
@@ -341,7 +395,9 @@ class Model:
         """keras Model.fit_generator (main.py:126-132): generator yields (x, y) batches.
 
         Epoch loss/acc are means over samples (per-step values weighted by batch size,
-        as Keras does).  A generator exposing ``last_global_batch`` (the rank-sharded
+        as Keras does).  Compiled with 'psnr' / 'ssim', the validation logs gain val_psnr /
+        val_ssim; the training-batch logs do not (the training head never stores its
+        prediction).  A generator exposing ``last_global_batch`` (the rank-sharded
         ImageDataGenerator iterators, or a ``zip`` of two of them) gets global-batch-mean
         gradients under data parallelism (see train_on_batch).  ``distributed=True`` (or None with an initialised process group
         of more than one rank) trains data-parallel: each rank consumes its own
@@ -373,14 +429,7 @@ class Model:
             tot = self._allreduce_sum(tot)
             logs = {"loss": tot[0] / tot[2], "acc": tot[1] / tot[2]}
             if validation_data is not None:
-                vt = np.zeros(3)
-                vsteps = validation_steps or 1
-                for _ in range(vsteps):
-                    xv, yv = next(validation_data) if hasattr(validation_data, "__next__") else validation_data
-                    vt[:2] += np.asarray(self.evaluate(xv, yv, batch_size=len(xv))) * len(xv)
-                    vt[2] += len(xv)
-                vt = self._allreduce_sum(vt)
-                logs["val_loss"], logs["val_acc"] = vt[0] / vt[2], vt[1] / vt[2]
+                logs.update(self._validation_logs(validation_data, validation_steps))
             if verbose and rank == 0:
                 msg = " - ".join(f"{k}: {v:.4f}" for k, v in logs.items())
                 print(f"Epoch {epoch + 1}/{epochs} - {time.time() - t0:.1f}s - {msg}", file=sys.stderr)

@@ -409,3 +409,27 @@ def augment_affine(src, mats, flips, scale, dst):
     assert mats.dtype == torch.float64 and flips.dtype == torch.int32 and mats.numel() == 6 * n
     call("cnnitmo_augment_affine", 1 if src.dtype == torch.uint8 else 0, ptr(src), n, h, w, c, ptr(mats),
          ptr(flips), float(scale), ptr(dst), stream_ptr())
+
+
+# ---------------------------------------------------------------- image metrics
+MSE_PSNR = 1
+SSIM = 2
+
+
+def image_metrics_workspace_bytes(n, h, w):
+    return query("cnnitmo_image_metrics_workspace_bytes", n, h, w)
+
+
+def image_metrics(what, a, b, max_val=1.0, out=None):
+    """a, b [n,h,w,3] contiguous fp32 device tensors -> out [n,3] fp64 = (mse, psnr dB, ssim) per
+    image (cnnitmo_image_metrics); what = MSE_PSNR | SSIM, columns not asked for are left as they
+    are (NaN in a fresh out)."""
+    n, h, w, c = a.shape
+    assert c == 3 and tuple(b.shape) == (n, h, w, 3), (tuple(a.shape), tuple(b.shape))
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    if out is None:
+        out = torch.full((n, 3), float("nan"), dtype=torch.float64, device=a.device)
+    ws = workspace(image_metrics_workspace_bytes(n, h, w), a.device)
+    call("cnnitmo_image_metrics", what, ptr(a), ptr(b), n, h, w, float(max_val), ptr(out), ws.data_ptr(),
+         ws.numel(), stream_ptr())
+    return out

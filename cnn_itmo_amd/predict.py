@@ -10,7 +10,8 @@ Here the same conventions run batched on the GPU:
 
     python -m cnn_itmo_amd.predict --model saved7-model-218-0.73.hdf5 \\
         [--input images_to_predict/input] [--output images_to_predict/output] \\
-        [--batch 8] [--dtype float32|bfloat16] [--tile TH,TW]
+        [--batch 8] [--dtype float32|bfloat16] [--tile TH,TW] \\
+        [--reference ground_truth_dir [--metrics-csv scores.csv]]
 
 Differences, all deliberate: images are processed in sorted order, in batches
 of equal-sized frames; the output file name is the input's base name (the
@@ -100,7 +101,24 @@ def predict_frames(model, frames_u8, batch=8, cache=None, tile=None):
     return outs
 
 
-def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None):
+def score_png(pred_u8, ref_path):
+    """(psnr dB, ssim) of a written uint8 prediction against the PNG at ref_path, on the 0..255
+    values (max_val 255): what measuring the two files gives."""
+    from . import metrics
+    ref = np.array(read_png(ref_path))  # (a writable copy: PIL's buffer is read-only)
+    if ref.shape != pred_u8.shape:
+        raise ValueError(f"{ref_path}: reference is {ref.shape[1]}x{ref.shape[0]}, the prediction "
+                         f"{pred_u8.shape[1]}x{pred_u8.shape[0]}")
+    ps, ss = metrics.psnr_ssim(pred_u8, ref, max_val=255.0)
+    return float(ps.item()), float(ss.item())
+
+
+def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None, reference=None,
+                metrics_csv=None):
+    """``reference``: a directory of ground-truth PNGs; every written prediction is scored
+    against the file of the same name there (PSNR / SSIM, logged per file and as the mean; a
+    missing reference is reported and skipped, a size mismatch raises).  ``metrics_csv``:
+    also write ``name;psnr;ssim`` rows to that file."""
     from PIL import Image
     files = sorted(glob.glob(os.path.join(in_dir, pattern)))
     if not files:
@@ -112,6 +130,7 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
         groups.setdefault(frames[f].shape, []).append(f)
     cache = {}
     written = []
+    scores = []
     for shape, fs in groups.items():
         log(f"Grabbing {len(fs)} input files of {shape[1]}x{shape[0]}")
         preds = predict_frames(model, [frames[f] for f in fs], batch, cache, tile)
@@ -119,6 +138,23 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
             dst = os.path.join(out_dir, os.path.basename(f))
             Image.fromarray(p).save(dst)
             written.append(dst)
+            if reference is not None:
+                ref = os.path.join(reference, os.path.basename(f))
+                if not os.path.exists(ref):
+                    log(f"{os.path.basename(f)}: no reference {ref}, not scored")
+                    continue
+                ps, ss = score_png(p, ref)
+                log(f"{os.path.basename(f)}: psnr {ps:.4f} dB, ssim {ss:.6f}")
+                scores.append((os.path.basename(f), ps, ss))
+    if reference is not None:
+        if scores:
+            log(f"mean of {len(scores)} scored files: psnr {np.mean([s[1] for s in scores]):.4f} dB, "
+                f"ssim {np.mean([s[2] for s in scores]):.6f}")
+        if metrics_csv:
+            with open(metrics_csv, "w", newline="") as fh:
+                fh.write("name;psnr;ssim\n")
+                for name, ps, ss in scores:
+                    fh.write(f"{name};{ps:.10g};{ss:.10g}\n")
     return written
 
 
@@ -130,14 +166,20 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"])
     ap.add_argument("--tile", default=None, help="TH,TW: spatially tiled inference (multiples of 16; 96-px halos)")
+    ap.add_argument("--reference", default=None,
+                    help="directory of ground-truth PNGs: score each written PNG against the same-named file "
+                         "(PSNR and SSIM of the 8-bit images)")
+    ap.add_argument("--metrics-csv", default=None, help="with --reference: write name;psnr;ssim rows to this file")
     a = ap.parse_args(argv)
+    if a.metrics_csv and not a.reference:
+        ap.error("--metrics-csv needs --reference")
     tile = tuple(int(v) for v in a.tile.split(",")) if a.tile else None
     from .model import load_model
     m = load_model(a.model)
     if m.optimizer is None:
         m.compile(optimizer="rmsprop", loss="mse", metrics=["accuracy"])
     m.set_dtype(a.dtype)
-    out = predict_dir(m, a.input, a.output, a.batch, tile=tile)
+    out = predict_dir(m, a.input, a.output, a.batch, tile=tile, reference=a.reference, metrics_csv=a.metrics_csv)
     print(f"wrote {len(out)} predictions to {a.output}")
     return 0
 

@@ -478,6 +478,25 @@ int cnnitmo_tonemap_apply(int curve, const float* hdr, int n, int h, int w, cons
 int cnnitmo_inverse_reinhard_apply(int mode, const void* sdr, int n, int h, int w, const double* lum_coef,
                                    const double* stats, double a, double g, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Image-fidelity metrics of two NHWC RGB batches a, b (fp32 [n][h][w][3],
+ * contiguous), per image, with dynamic range max_val:
+ *   mse  = mean over h*w*3 of (a-b)^2;  psnr = 10*log10(max_val^2 / mse)
+ *          (tf.image.psnr; mse == 0 gives +inf);
+ *   ssim = tf.image.ssim defaults (Wang et al. 2004): 11x11 Gaussian window,
+ *          sigma 1.5, valid positions only, K1 0.01, K2 0.03, biased weighted
+ *          moments, mean over the (h-10)*(w-10) positions and the 3 channels.
+ * what: bit 0 = MSE/PSNR, bit 1 = SSIM.  out (device): double [n][3] =
+ * {mse, psnr_dB, ssim}; entries not asked for are left untouched.  One pass over
+ * both images, moment sums in fp64, fixed-order two-level reduction (bitwise
+ * reproducible, no atomics).  The SSIM bit needs h >= 11 and w >= 11.
+ * workspace: cnnitmo_image_metrics_workspace_bytes(n, h, w) bytes of device
+ * memory (<= 0 for a bad shape; needs no GPU).
+ */
+long cnnitmo_image_metrics_workspace_bytes(int n, int h, int w);
+int cnnitmo_image_metrics(int what, const float* a, const float* b, int n, int h, int w, double max_val,
+                          double* out, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
