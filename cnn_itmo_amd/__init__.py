@@ -6,12 +6,13 @@ include/cnn_itmo.h).  No CPU fallback: the engine raises without a ROCm GPU.
 """
 from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2DTranspose, Dropout,
                      Input, InputLayer, MaxPooling2D, clear_session, concatenate)
-from .model import Model, RMSprop, load_model
+from .model import Model, load_model
+from .optimizers import SGD, Adam, RMSprop
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import CSVLogger, LambdaCallback, ModelCheckpoint
 from . import metrics
 
 __all__ = ["Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
-           "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
+           "Adam", "SGD", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
            "LambdaCallback", "ModelCheckpoint", "metrics"]

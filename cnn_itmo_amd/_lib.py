@@ -22,6 +22,8 @@ NO_BN = 2
 PARITY = 4
 BIAS_PER_COL = 8
 CONSUMER_ROWS = 64
+# CNNITMO_LOSS_*: canonical loss name -> id
+LOSSES = {"mse": 0, "mae": 1, "logcosh": 2, "msle": 3, "binary_crossentropy": 4}
 
 vp = C.c_void_p
 i32 = C.c_int
@@ -117,6 +119,10 @@ SIGNATURES = {
     "cnnitmo_tconv2x2_dgrad_bn_kernel_name": (C.c_char_p, [i32] * 6),
     "cnnitmo_border_sums": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
     "cnnitmo_rmsprop": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp]),
+    "cnnitmo_head_fwd_bwd_loss": (i32, [i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64,
+                                        vp]),
+    "cnnitmo_adam": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
+    "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),
 }
 
 

@@ -771,8 +771,9 @@ extern "C" int cnnitmo_pool_bnsums(int dtype, const void* dyp, const uint8_t* id
 }
 
 // ----------------------------------------------------------------------------
-// Head: Conv2D(3, 1, activation='sigmoid') + MSE + categorical accuracy
-// (model.py:276,281).  LPP = cin/VE lanes share one pixel.
+// Head: Conv2D(3, 1, activation='sigmoid') + the training loss (MSE, model.py:281, or
+// another CNNITMO_LOSS_*: loss_term below) + categorical accuracy (model.py:276,281).
+// LPP = cin/VE lanes share one pixel.
 // part row layout: [loss, correct, db0..2, dW[3][cin]]
 // ----------------------------------------------------------------------------
 static constexpr int HEAD_BLOCKS = 1024;
@@ -783,7 +784,37 @@ extern "C" int cnnitmo_head_rows(long p) {
   return (int)std::max<long>(1, std::min<long>(HEAD_BLOCKS, (p + 31) / 32));
 }
 
-template <typename T, bool BWD>
+// The training loss of one output element (cnn_itmo.h, CNNITMO_LOSS_*): its term l and
+// g = dl/dz, z the head's logit, y = sigmoid(z), t the target; fp32, without the 1/numel
+// of the mean.  Both head kernels call this and nothing else differs between the losses.
+template <int LOSS>
+__device__ __forceinline__ void loss_term(float z, float y, float t, float& l, float& g) {
+  if constexpr (LOSS == CNNITMO_LOSS_MSE) {
+    const float e = y - t;
+    l = e * e;
+    g = 2.f * e * y * (1.f - y);
+  } else if constexpr (LOSS == CNNITMO_LOSS_MAE) {
+    const float e = y - t;
+    l = fabsf(e);
+    g = (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) * y * (1.f - y);
+  } else if constexpr (LOSS == CNNITMO_LOSS_LOGCOSH) {
+    // ln cosh x = |x| + log1p(exp(-2|x|)) - ln 2 (Keras: x + softplus(-2x) - ln 2)
+    const float e = y - t, a = fabsf(e);
+    l = a + log1pf(expf(-2.f * a)) - 0.69314718055994531f;
+    g = tanhf(e) * y * (1.f - y);
+  } else if constexpr (LOSS == CNNITMO_LOSS_MSLE) {
+    const float a = logf(fmaxf(y, 1e-7f) + 1.f), b = logf(fmaxf(t, 1e-7f) + 1.f);
+    l = (a - b) * (a - b);
+    g = y >= 1e-7f ? 2.f * (a - b) / (y + 1.f) * y * (1.f - y) : 0.f;
+  } else {
+    // binary cross-entropy on the unclipped logit (Keras clips y to [1e-7, 1-1e-7] first)
+    static_assert(LOSS == CNNITMO_LOSS_BCE, "unknown loss");
+    l = fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
+    g = y - t;
+  }
+}
+
+template <typename T, bool BWD, int LOSS = CNNITMO_LOSS_MSE>
 __global__ void head_kernel(const T* __restrict__ x, int N, int H, int Hv, int W, int cin,
                             const float* __restrict__ wt, const float* __restrict__ bias,
                             const float* __restrict__ target, float* __restrict__ yhat,
@@ -880,16 +911,19 @@ __global__ void head_kernel(const T* __restrict__ x, int N, int H, int Hv, int W
       float dz[3] = {0.f, 0.f, 0.f};
       if (valid[u]) {
         const float t0 = tg[u][0], t1 = tg[u][1], t2 = tg[u][2];
-        const float e0 = yh[0] - t0, e1 = yh[1] - t1, e2 = yh[2] - t2;
+        float l0, l1, l2, g0, g1, g2;
+        loss_term<LOSS>(z[0], yh[0], t0, l0, g0);
+        loss_term<LOSS>(z[1], yh[1], t1, l1, g1);
+        loss_term<LOSS>(z[2], yh[2], t2, l2, g2);
         if (sub == 0) {
-          lsum += e0 * e0 + e1 * e1 + e2 * e2;
+          lsum += l0 + l1 + l2;
           const int at = (t1 > t0) ? ((t2 > t1) ? 2 : 1) : ((t2 > t0) ? 2 : 0);
           const int ap = (yh[1] > yh[0]) ? ((yh[2] > yh[1]) ? 2 : 1) : ((yh[2] > yh[0]) ? 2 : 0);
           corr += (at == ap) ? 1.f : 0.f;
         }
-        dz[0] = 2.f * e0 * yh[0] * (1.f - yh[0]) * inv_numel;
-        dz[1] = 2.f * e1 * yh[1] * (1.f - yh[1]) * inv_numel;
-        dz[2] = 2.f * e2 * yh[2] * (1.f - yh[2]) * inv_numel;
+        dz[0] = g0 * inv_numel;
+        dz[1] = g1 * inv_numel;
+        dz[2] = g2 * inv_numel;
       }
       if (sub == 0) {
         db[0] += dz[0]; db[1] += dz[1]; db[2] += dz[2];
@@ -973,7 +1007,7 @@ __device__ __forceinline__ void unpack16(const uint4& q, float* v) {
 }
 
 // BWD: loss + gradients; G3: the gradient leaves as g3 [P][3] (else dx = dz . W)
-template <typename T, int LPP, bool BWD, bool G3>
+template <typename T, int LPP, bool BWD, bool G3, int LOSS = CNNITMO_LOSS_MSE>
 __global__ __launch_bounds__(256) void head2_kernel(const T* __restrict__ x, int H, int Hv, int W, long P,
                                                     const float* __restrict__ wt, const float* __restrict__ bias,
                                                     const float* __restrict__ target, float* __restrict__ yhat,
@@ -1075,14 +1109,17 @@ __global__ __launch_bounds__(256) void head2_kernel(const T* __restrict__ x, int
     }
     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
     if (valid) {
-      const float e0 = y0 - t0, e1 = y1 - t1, e2 = y2 - t2;
-      lsum += e0 * e0 + e1 * e1 + e2 * e2;
+      float l0, l1, l2, g0, g1, g2;
+      loss_term<LOSS>(z.x + b0, y0, t0, l0, g0);
+      loss_term<LOSS>(z.y + b1, y1, t1, l1, g1);
+      loss_term<LOSS>(z.z + b2, y2, t2, l2, g2);
+      lsum += l0 + l1 + l2;
       const int at = (t1 > t0) ? ((t2 > t1) ? 2 : 1) : ((t2 > t0) ? 2 : 0);
       const int ap = (y1 > y0) ? ((y2 > y1) ? 2 : 1) : ((y2 > y0) ? 2 : 0);
       corr += (at == ap) ? 1.f : 0.f;
-      d0 = 2.f * e0 * y0 * (1.f - y0) * inv_numel;
-      d1 = 2.f * e1 * y1 * (1.f - y1) * inv_numel;
-      d2 = 2.f * e2 * y2 * (1.f - y2) * inv_numel;
+      d0 = g0 * inv_numel;
+      d1 = g1 * inv_numel;
+      d2 = g2 * inv_numel;
     }
     db0 += d0;
     db1 += d1;
@@ -1148,7 +1185,7 @@ __global__ __launch_bounds__(256) void head2_kernel(const T* __restrict__ x, int
 }
 
 // head2_kernel for this dtype / width, or false (head_kernel then)
-template <bool BWD>
+template <bool BWD, int LOSS = CNNITMO_LOSS_MSE>
 static bool launch_head2(int dtype, const void* x, int n, int h, int h_valid, int w, int cin, const float* wt,
                          const float* b, const float* target, float* yhat, void* dx, float inv_numel,
                          float* part, const float* scale, const float* shift, float* g3, int G_, hipStream_t s) {
@@ -1157,7 +1194,7 @@ static bool launch_head2(int dtype, const void* x, int n, int h, int h_valid, in
   // 32-bit pixel and target-byte offsets inside the kernel
   if (P >= (1L << 30) || (long)n * h_valid * w * 12 >= (1L << 31)) return false;
 #define H2K(T, L, G)                                                                                          \
-  hipLaunchKernelGGL((head2_kernel<T, L, BWD, G>), dim3(G_), dim3(256), 0, s, (const T*)x, h, h_valid, w, P, wt, \
+  hipLaunchKernelGGL((head2_kernel<T, L, BWD, G, LOSS>), dim3(G_), dim3(256), 0, s, (const T*)x, h, h_valid, w, P, wt, \
                      b, target, yhat, (T*)dx, inv_numel, part, scale, shift, g3)
 #define H2(T, L)                  \
   do {                            \
@@ -1204,9 +1241,10 @@ extern "C" int cnnitmo_head_fwd(int dtype, const void* x, int n, int h, int h_va
   return cnnitmo_check_launch("head_fwd");
 }
 
-static int head_fwd_bwd(int dtype, const void* x, int n, int h, int h_valid, int w, int cin, const float* wt,
-                        const float* b, const float* scale, const float* shift, const float* target, void* dx,
-                        float* g3, float* part, double grad_numel, void* stream) {
+template <int LOSS>
+static int head_fwd_bwd_t(int dtype, const void* x, int n, int h, int h_valid, int w, int cin, const float* wt,
+                          const float* b, const float* scale, const float* shift, const float* target, void* dx,
+                          float* g3, float* part, double grad_numel, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int VE = dtype == CNNITMO_BF16 ? 8 : 4;
   CNN_REQUIRE(cin % VE == 0 && (cin / VE) <= 64 && ((cin / VE) & (cin / VE - 1)) == 0,
@@ -1216,16 +1254,38 @@ static int head_fwd_bwd(int dtype, const void* x, int n, int h, int h_valid, int
   const int G = cnnitmo_head_rows(P);
   const double numel = grad_numel > 0.0 ? grad_numel : (double)n * h_valid * w * 3;
   const float inv_numel = (float)(1.0 / numel);
-  if (launch_head2<true>(dtype, x, n, h, h_valid, w, cin, wt, b, target, nullptr, dx, inv_numel, part, scale,
-                         shift, g3, G, s))
+  if (launch_head2<true, LOSS>(dtype, x, n, h, h_valid, w, cin, wt, b, target, nullptr, dx, inv_numel, part, scale,
+                               shift, g3, G, s))
     return cnnitmo_check_launch("head_fwd_bwd");
   if (dtype == CNNITMO_BF16)
-    hipLaunchKernelGGL((head_kernel<bf16, true>), dim3(G), dim3(256), 0, s, (const bf16*)x, n, h,
+    hipLaunchKernelGGL((head_kernel<bf16, true, LOSS>), dim3(G), dim3(256), 0, s, (const bf16*)x, n, h,
                        h_valid, w, cin, wt, b, target, nullptr, (bf16*)dx, inv_numel, part, scale, shift, g3);
   else
-    hipLaunchKernelGGL((head_kernel<float, true>), dim3(G), dim3(256), 0, s, (const float*)x, n, h,
+    hipLaunchKernelGGL((head_kernel<float, true, LOSS>), dim3(G), dim3(256), 0, s, (const float*)x, n, h,
                        h_valid, w, cin, wt, b, target, nullptr, (float*)dx, inv_numel, part, scale, shift, g3);
   return cnnitmo_check_launch("head_fwd_bwd");
+}
+
+extern "C" int cnnitmo_head_fwd_bwd_loss(int loss, int dtype, const void* x, int n, int h, int h_valid, int w, int cin,
+                                         const float* wt, const float* b, const float* scale, const float* shift,
+                                         const float* target, void* dx, float* g3, float* part, double grad_numel,
+                                         void* stream) {
+  CNN_REQUIRE(loss >= CNNITMO_LOSS_MSE && loss <= CNNITMO_LOSS_BCE, "head_fwd_bwd_loss: unknown loss %d", loss);
+  CNN_REQUIRE((dx != nullptr) != (g3 != nullptr), "head_fwd_bwd_loss: exactly one of dx and g3 must be given");
+#define HEAD_LOSS(L)                                                                                              \
+  case L:                                                                                                         \
+    return head_fwd_bwd_t<L>(dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, dx, g3, part, grad_numel, \
+                             stream)
+  switch (loss) {
+    HEAD_LOSS(CNNITMO_LOSS_MAE);
+    HEAD_LOSS(CNNITMO_LOSS_LOGCOSH);
+    HEAD_LOSS(CNNITMO_LOSS_MSLE);
+    HEAD_LOSS(CNNITMO_LOSS_BCE);
+    default: break;
+  }
+#undef HEAD_LOSS
+  return head_fwd_bwd_t<CNNITMO_LOSS_MSE>(dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, dx, g3, part,
+                                          grad_numel, stream);
 }
 
 extern "C" int cnnitmo_head_fwd_bwd(int dtype, const void* x, int n, int h, int h_valid, int w,
@@ -1233,8 +1293,8 @@ extern "C" int cnnitmo_head_fwd_bwd(int dtype, const void* x, int n, int h, int 
                                     const float* shift, const float* target, void* dx, float* part,
                                     double grad_numel, void* stream) {
   CNN_REQUIRE(dx, "head_fwd_bwd: null dx");
-  return head_fwd_bwd(dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, dx, nullptr, part, grad_numel,
-                      stream);
+  return cnnitmo_head_fwd_bwd_loss(CNNITMO_LOSS_MSE, dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, dx,
+                                   nullptr, part, grad_numel, stream);
 }
 
 extern "C" int cnnitmo_head_fwd_bwd_g3(int dtype, const void* x, int n, int h, int h_valid, int w, int cin,
@@ -1242,8 +1302,8 @@ extern "C" int cnnitmo_head_fwd_bwd_g3(int dtype, const void* x, int n, int h, i
                                        const float* target, float* g3, float* part, double grad_numel,
                                        void* stream) {
   CNN_REQUIRE(g3, "head_fwd_bwd_g3: null g3");
-  return head_fwd_bwd(dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, nullptr, g3, part, grad_numel,
-                      stream);
+  return cnnitmo_head_fwd_bwd_loss(CNNITMO_LOSS_MSE, dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target,
+                                   nullptr, g3, part, grad_numel, stream);
 }
 
 // Folded input BN (x = r, y = r*s + h): dW[o][c] = s[c]*sum(dz*r) + h[c]*db[o].
@@ -1317,6 +1377,92 @@ extern "C" int cnnitmo_rmsprop(float* p, const float* g, float* a, long n, float
   hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0,
                      (hipStream_t)stream, p, g, a, n, lr, rho, eps, grad_scale);
   return cnnitmo_check_launch("rmsprop");
+}
+
+// ----------------------------------------------------------------------------
+// Adam and SGD (Keras 2.2 arithmetic, cnn_itmo.h) over the same flat buffers: one pass,
+// float4 body and scalar tail like rmsprop_kernel.
+// ----------------------------------------------------------------------------
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr_t, float b1, float b2,
+                                            float eps) {
+  m = b1 * m + (1.f - b1) * g;
+  v = b2 * v + (1.f - b2) * g * g;
+  p -= lr_t * m / (sqrtf(v) + eps);
+}
+
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, long n, float lr_t, float b1, float b2, float eps, float gs) {
+  const long n4 = n / 4;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
+       i += (long)gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    float* pp = &pv.x;
+    const float* gg = &gv.x;
+    float* mm = &mv.x;
+    float* vq = &vv.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) adam_update(pp[e], gg[e] * gs, mm[e], vq[e], lr_t, b1, b2, eps);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x)
+    adam_update(p[i], g[i] * gs, m[i], v[i], lr_t, b1, b2, eps);
+}
+
+extern "C" int cnnitmo_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, float beta1,
+                            float beta2, float eps, float grad_scale, void* stream) {
+  CNN_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+              "adam: buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m,
+                     v, n, lr_t, beta1, beta2, eps, grad_scale);
+  return cnnitmo_check_launch("adam");
+}
+
+template <bool NESTEROV>
+__device__ __forceinline__ void sgd_update(float& p, float g, float& mom, float lr, float mu) {
+  mom = mu * mom - lr * g;
+  if constexpr (NESTEROV) p = p + mu * mom - lr * g;
+  else p = p + mom;
+}
+
+template <bool NESTEROV>
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom, long n,
+                           float lr, float mu, float gs) {
+  const long n4 = n / 4;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
+       i += (long)gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(mom)[i];
+    float* pp = &pv.x;
+    const float* gg = &gv.x;
+    float* mm = &mv.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sgd_update<NESTEROV>(pp[e], gg[e] * gs, mm[e], lr, mu);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(mom)[i] = mv;
+  }
+  for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x)
+    sgd_update<NESTEROV>(p[i], g[i] * gs, mom[i], lr, mu);
+}
+
+extern "C" int cnnitmo_sgd(float* p, const float* g, float* mom, long n, float lr, float momentum, int nesterov,
+                           float grad_scale, void* stream) {
+  CNN_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)mom) % 16 == 0, "sgd: buffers must be 16-byte aligned");
+  const dim3 grid(grid_for(n / 4 + 1, 256, 2048));
+  if (nesterov)
+    hipLaunchKernelGGL(sgd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, mom, n, lr, momentum,
+                       grad_scale);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, mom, n, lr, momentum,
+                       grad_scale);
+  return cnnitmo_check_launch("sgd");
 }
 
 // ----------------------------------------------------------------------------

@@ -164,12 +164,13 @@ class GradBucketer:
 
 def broadcast_state(engine, src=0, group=None):
     """DDP-style start: every rank takes rank `src`'s parameters, moving statistics,
-    RMSprop accumulators and step counter."""
-    for t in (engine.params, engine.bufs, engine.accum):
+    optimizer slots (as many as rank `src` holds) and the step / iterations counters."""
+    cnt = torch.tensor([engine.step, engine.iterations, len(engine.slots)], dtype=torch.float64,
+                       device=engine.params.device)
+    dist.broadcast(cnt, src, group=group)
+    engine.step, engine.iterations, nslots = (int(v) for v in cnt.tolist())
+    for t in [engine.params, engine.bufs] + engine.ensure_slots(nslots)[:nslots]:
         dist.broadcast(t, src, group=group)
-    step = torch.tensor([engine.step], dtype=torch.float64, device=engine.params.device)
-    dist.broadcast(step, src, group=group)
-    engine.step = int(step.item())
     engine.weights_dirty = True
 
 

@@ -11,7 +11,7 @@ needs; anything else raises NotImplementedError at compile time):
   MaxPooling2D(2)                                -> PoolStage
   concatenate([...])                             -> ConcatStage (zero-copy: inputs are placed
                                                     as channel slices of one buffer)
-  final Conv2D(3, 1, activation='sigmoid')       -> HeadStage (sigmoid + MSE + accuracy + grads)
+  final Conv2D(3, 1, activation='sigmoid')       -> HeadStage (sigmoid + loss + accuracy + grads)
 
 Training BN uses per-replica batch statistics (Keras semantics per process).
 
@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import optimizers as O
 from . import _lib as L
 from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2DTranspose, Dropout,
                      InputLayer, MaxPooling2D)
@@ -699,23 +700,33 @@ class HeadStage(Stage):
                 and prod.bn is not None and prod.drop is None and prod.kind == "c3")
 
     def loss_and_grad(self, n, target, loss_acc, grad_numel=0.0):
-        """grad_numel: the MSE gradient's normaliser (0: this batch's element count)."""
+        """The model's loss (Engine.loss_id), 'accuracy' and the head's gradients.
+        grad_numel: the loss gradient's normaliser (0: this batch's element count)."""
         e = self.eng
         P = n * self.vin.h * self.vin.w
         rows = ops.head_rows(P)
         part = torch.empty(rows * (5 + 3 * self.cin), device=e.device, dtype=torch.float32)
         aff = self.vin.coef() if e.training and self.vin.folded else None
         wt = e.p(self.name + "/kernel")
+        loss = e.loss_id  # 'mse' keeps its own entry points (the same kernels)
         if self._rank3():
             g3 = torch.empty(P * 3, device=e.device, dtype=torch.float32)
-            ops.head_fwd_bwd_g3(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, g3,
-                                part, aff, grad_numel)
+            if loss == L.LOSSES["mse"]:
+                ops.head_fwd_bwd_g3(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, g3,
+                                    part, aff, grad_numel)
+            else:
+                ops.head_fwd_bwd_loss(loss, e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target,
+                                      part, g3=g3, aff=aff, grad_numel=grad_numel)
             self.vin.grad_g3 = (g3, wt)
         else:
             self.vin.ensure_grad(n, e.tdtype, e.device)
             dx = self.vin.gview(n)
-            ops.head_fwd_bwd(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, dx.buf,
-                             part, aff, grad_numel)
+            if loss == L.LOSSES["mse"]:
+                ops.head_fwd_bwd(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, dx.buf,
+                                 part, aff, grad_numel)
+            else:
+                ops.head_fwd_bwd_loss(loss, e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target,
+                                      part, dx=dx.buf, aff=aff, grad_numel=grad_numel)
         v = self.vin
         raw = torch.empty(3 * self.cin, device=e.device, dtype=torch.float32) \
             if e.training and v.sum_consumers and v.folded else None
@@ -905,7 +916,11 @@ class Engine:
         self.nparams = off
         self.params = torch.zeros(off, device=self.device, dtype=torch.float32)
         self.grads = torch.zeros(off, device=self.device, dtype=torch.float32)
+        # optimizer state: flat slot buffers shaped like params (optimizers.py); slot 0 is
+        # `accum` (RMSprop's accumulators, SGD's moments, Adam's m), further slots on demand
         self.accum = torch.zeros(off, device=self.device, dtype=torch.float32)
+        self.slots = [self.accum]
+        self.iterations = 0  # APPLIED updates (step also counts apply=False calls and seeds Dropout)
         self.bufs = torch.zeros(max(boff, 1), device=self.device, dtype=torch.float32)
         for st in self.stages:
             st.bind(self)
@@ -993,6 +1008,18 @@ class Engine:
             return
         prod.head = head
         head.fused = True
+
+    # ---- loss / optimizer state ---------------------------------------------
+    @property
+    def loss_id(self):
+        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile)."""
+        return L.LOSSES[getattr(self.model, "loss", None) or "mse"]
+
+    def ensure_slots(self, k):
+        """At least k optimizer slot buffers (new ones zero, as Keras creates them)."""
+        while len(self.slots) < k:
+            self.slots.append(torch.zeros_like(self.accum))
+        return self.slots
 
     # ---- parameter access ---------------------------------------------------
     def _slice(self, flat, table, key):
@@ -1087,9 +1114,12 @@ class Engine:
         self._release()
         return yhat
 
-    def train_step(self, x, target, seed=None, lr=1e-3, rho=0.9, eps=1e-7, grad_scale=1.0,
-                   sync=None, apply=True, grad_frames=None):
-        """One fwd+bwd+RMSprop step.  Returns a device tensor [loss, acc] (this batch's means).
+    def train_step(self, x, target, seed=None, optimizer=None, grad_scale=1.0, sync=None, apply=True,
+                   grad_frames=None, lr=1e-3, rho=0.9, eps=1e-7):
+        """One fwd+bwd+update step.  Returns a device tensor [loss, acc] (this batch's means).
+        optimizer: an optimizers.Optimizer (or what optimizers.get takes); without one,
+        RMSprop(lr, rho, eps).  The update runs with this engine's slots and `iterations`,
+        which only an applied update advances.
         grad_frames: the frame count the loss gradient is normalised by (default: this
         batch's).  Data parallel with unequal shares, global_frames / world makes the
         averaged gradient that of the global batch mean (Model.train_on_batch)."""
@@ -1114,7 +1144,9 @@ class Engine:
         if sync is not None:
             sync()
         if apply:
-            ops.rmsprop(self.params, self.grads, self.accum, lr, rho, eps, grad_scale)
+            opt = O.RMSprop(lr=lr, rho=rho, epsilon=eps) if optimizer is None else O.get(optimizer)
+            opt.apply(self.params, self.grads, self.ensure_slots(opt.slots), self.iterations, grad_scale)
+            self.iterations += 1
             self.weights_dirty = True
         self.step += 1
         return loss_acc

@@ -13,10 +13,13 @@ checkpoint written here loads in Keras:
   /model_weights/<layer>            attrs weight_names ['<layer>/kernel:0', ...]
   /model_weights/<layer>/<layer>/kernel:0   dataset (Keras layout: Conv2D HWIO,
                                             Conv2DTranspose (kh, kw, Cout, Cin))
-  /optimizer_weights    attrs weight_names; RMSprop accumulators, one per
-                        trainable weight in model order (Keras 2.2.4
-                        ``RMSprop.weights``; a leading ``iterations`` scalar,
-                        as later Keras versions write, is accepted on load)
+  /optimizer_weights    attrs weight_names; Keras 2.2.4's ``optimizer.weights``, each
+                        slot one tensor per trainable weight in model order:
+                        RMSprop the accumulators (a leading ``iterations`` scalar,
+                        as later Keras versions write, is accepted on load), SGD
+                        [iterations] + moments, Adam [iterations] + ms + vs + one
+                        shape-(1,) zero per weight (the vhats without amsgrad;
+                        optional on load).  Read by order and shape, not by name.
 
 model_config is the Keras functional-API config ({"class_name": "Model",
 "config": {"layers": [...], "input_layers", "output_layers"}}); every layer
@@ -122,9 +125,8 @@ def training_config(model):
     o = model.optimizer
     # the compiled metrics in order ('accuracy', 'psnr', 'ssim'); load_model compiles with them
     metrics = [_METRIC_CONFIG[k] for k in getattr(model, "metrics_names", [])[1:]]
-    return {"optimizer_config": {"class_name": "RMSprop",
-                                 "config": {"lr": o.lr, "rho": o.rho, "decay": 0.0, "epsilon": o.epsilon}},
-            "loss": "mse", "metrics": metrics,
+    return {"optimizer_config": {"class_name": o.class_name, "config": o.get_config()},
+            "loss": model.loss, "metrics": metrics,
             "sample_weight_mode": None, "loss_weights": None}
 
 
@@ -156,14 +158,27 @@ def save_model_hdf5(model, path, include_optimizer=True, weights_only=False):
         g.attrs["weight_names"] = names if names else np.zeros((0,), dtype="S1")
     if not weights_only and include_optimizer and model.optimizer is not None:
         w.attrs["training_config"] = json.dumps(training_config(model))
-        accum = model.named_accumulators()
-        if accum is not None:
+        slots = model.named_slots()
+        if slots is not None:
+            # Keras 2.2.4's optimizer.weights order; the reader goes by order and shape alone
+            cls = model.optimizer.class_name
             og = w.create_group("optimizer_weights")
+            vals = []
+            if cls != "RMSprop":
+                vals.append(np.asarray(model.iterations, np.int64))
+            for slot in slots[:model.optimizer.slots]:
+                vals += [_to_keras(l, wname, slot[f"{l.name}/{wname}"]).astype(np.float32) for l, wname in trainable]
+            if cls == "Adam":  # the vhats of a non-amsgrad Adam: one zero of shape (1,) per weight
+                vals += [np.zeros((1,), np.float32) for _ in trainable]
             names = []
-            for i, (l, wname) in enumerate(trainable):
-                nm = "training/RMSprop/Variable%s:0" % ("" if i == 0 else f"_{i}")
+            for i, v in enumerate(vals):
+                if cls != "RMSprop" and i == 0:
+                    nm = f"{cls}/iterations:0"
+                else:
+                    k = i - (cls != "RMSprop")
+                    nm = f"training/{cls}/Variable%s:0" % ("" if k == 0 else f"_{k}")
                 names.append(nm)
-                og.create_dataset(nm, _to_keras(l, wname, accum[f"{l.name}/{wname}"]).astype(np.float32))
+                og.create_dataset(nm, v)
             og.attrs["weight_names"] = names
     w.save(path)
 
@@ -275,7 +290,8 @@ def load_weights_hdf5(model, path, by_name=False):
 
 def load_model_hdf5(path, compile=True):
     """keras.models.load_model for a Keras 2.2 HDF5 file (predict.py:24)."""
-    from .model import RMSprop, _to_internal
+    from . import optimizers
+    from .model import _to_internal
     f = hdf5.File(path)
     if "model_config" not in f.attrs:
         raise ValueError("No model found in config file.")
@@ -285,27 +301,32 @@ def load_model_hdf5(path, compile=True):
     if compile and "training_config" in f.attrs:
         tc = json.loads(_str(f.attrs["training_config"]))
         oc = tc.get("optimizer_config", {})
-        if oc.get("class_name", "RMSprop") != "RMSprop":
-            raise NotImplementedError(f"optimizer {oc.get('class_name')!r}")
-        o = oc.get("config", {})
-        if float(o.get("decay", 0.0)):
-            raise NotImplementedError("RMSprop decay is not on the path")
-        m.compile(RMSprop(lr=o.get("lr", o.get("learning_rate", 1e-3)), rho=o.get("rho", 0.9),
-                          epsilon=o.get("epsilon")), tc.get("loss", "mse"), tc.get("metrics") or ["accuracy"])
+        opt = optimizers.from_config(oc.get("class_name", "RMSprop"), oc.get("config", {}))
+        m.compile(opt, tc.get("loss", "mse"), tc.get("metrics") or ["accuracy"])
         if "optimizer_weights" in f:
+            # matched by order and shape, never by name: [iterations] + one tensor per trainable
+            # weight and slot (+ Adam's shape-(1,) vhat placeholders, with or without)
             og = f["optimizer_weights"]
             wn = _attr_chunks(og, "weight_names")
             vals = [og[n].read() for n in wn]
             train = [(l, wname, shp) for l in m.layers for wname, shp, tr in l.weight_shapes() if tr]
+            nt = len(train)
             step = 0
-            if len(vals) == len(train) + 1 and np.asarray(vals[0]).size == 1:
-                step = int(np.asarray(vals[0]).reshape(-1)[0])  # iterations (later Keras versions)
+            if len(vals) % nt == 1 and np.asarray(vals[0]).size == 1:
+                step = int(np.asarray(vals[0]).reshape(-1)[0])  # iterations (RMSprop: later Keras versions)
                 vals = vals[1:]
-            if len(vals) == len(train):
-                acc = {}
-                for (l, wname, shp), v in zip(train, vals):
-                    if tuple(v.shape) != tuple(shp):
-                        raise ValueError(f"optimizer weight for {l.name}/{wname}: {v.shape} != {tuple(shp)}")
-                    acc[f"{l.name}/{wname}"] = _to_internal(l, wname, np.asarray(v, np.float32))
-                m._pending_accum = ("named", acc, step)
+            if len(vals) == (opt.slots + 1) * nt and all(tuple(np.shape(v)) == (1,) for v in vals[opt.slots * nt:]):
+                vals = vals[:opt.slots * nt]
+            if len(vals) == opt.slots * nt:
+                slots = []
+                for s in range(opt.slots):
+                    d = {}
+                    for (l, wname, shp), v in zip(train, vals[s * nt:(s + 1) * nt]):
+                        if tuple(v.shape) != tuple(shp):
+                            raise ValueError(f"optimizer weight for {l.name}/{wname}: {v.shape} != {tuple(shp)}")
+                        d[f"{l.name}/{wname}"] = _to_internal(l, wname, np.asarray(v, np.float32))
+                    slots.append(d)
+                m._pending_accum = ("named", slots[0], step)
+                m._pending_slots = slots[1:]
+                m._pending_iterations = step
     return m

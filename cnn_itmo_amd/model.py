@@ -29,15 +29,15 @@ from .layers import (LAYER_CLASSES, BatchNormalization, Conv2D, Conv2DTranspose,
                      Layer)
 
 
-class RMSprop:
-    """keras.optimizers.RMSprop(lr=0.001, rho=0.9, epsilon=None->1e-7, decay=0)."""
+from . import optimizers
+from .optimizers import SGD, Adam, RMSprop  # noqa: F401  (keras.optimizers names, re-exported)
 
-    def __init__(self, lr=0.001, rho=0.9, epsilon=None, decay=0.0, **kwargs):
-        self.lr = float(kwargs.get("learning_rate", lr))
-        self.rho = float(rho)
-        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
-        if decay:
-            raise NotImplementedError("RMSprop decay is not on the path")
+# compile()'s loss names -> the canonical name (Model.loss, _lib.LOSSES)
+_LOSS_NAMES = {"mse": "mse", "MSE": "mse", "mean_squared_error": "mse",
+               "mae": "mae", "MAE": "mae", "mean_absolute_error": "mae",
+               "logcosh": "logcosh",
+               "msle": "msle", "MSLE": "msle", "mean_squared_logarithmic_error": "msle",
+               "binary_crossentropy": "binary_crossentropy"}
 
 
 _METRIC_KEYS = {"accuracy": "acc", "acc": "acc", "categorical_accuracy": "acc", "psnr": "psnr", "ssim": "ssim"}
@@ -98,6 +98,7 @@ class Model:
         self.layers = sorted(seen.values(), key=lambda l: l.seq)
         self._weights = {}  # internal-layout numpy weights (host copy, authoritative before engine)
         self.optimizer = None
+        self.loss = None         # canonical loss name once compiled
         self.engine = None
         self._dp = None          # dist.GradBucketer once distribute() was called
         self._dp_args = None
@@ -159,18 +160,26 @@ class Model:
 
     # ---- compile / engine ------------------------------------------------------
     def compile(self, optimizer="rmsprop", loss="mse", metrics=None, dtype=None, **kwargs):
-        if isinstance(optimizer, str):
-            if optimizer.lower() != "rmsprop":
-                raise NotImplementedError(f"optimizer {optimizer!r} (only 'rmsprop' is on the path)")
-            optimizer = RMSprop()
-        if loss not in ("mse", "mean_squared_error"):
-            raise NotImplementedError(f"loss {loss!r} (only 'mse' is on the path)")
+        """optimizer: 'rmsprop' / 'adam' / 'sgd' (any case) or an RMSprop / Adam / SGD instance;
+        loss: 'mse', 'mae', 'logcosh', 'msle', 'binary_crossentropy' or a Keras alias of one
+        (_LOSS_NAMES).  Nothing changes when an argument is refused."""
+        optimizer = optimizers.get(optimizer)
+        if not isinstance(loss, str) or loss not in _LOSS_NAMES:
+            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES)})")
+        if dtype not in (None, "float32", "bfloat16"):
+            raise ValueError("dtype must be 'float32' or 'bfloat16'")
         names = []
         for m in metrics or []:
             k = _metric_key(m)
             if k not in names:
                 names.append(k)
+        if self.engine is not None and self.optimizer is not None and type(optimizer) is not type(self.optimizer):
+            # another optimizer class starts from fresh state, as a new Keras optimizer does
+            for s in self.engine.slots:
+                s.zero_()
+            self.engine.iterations = 0
         self.optimizer = optimizer
+        self.loss = _LOSS_NAMES[loss]
         self.metrics_names = ["loss"] + names
         # 'psnr' / 'ssim' in the order given: computed by evaluate() and for the validation logs
         self.image_metrics = [k for k in names if k != "acc"]
@@ -182,13 +191,15 @@ class Model:
             raise ValueError("dtype must be 'float32' or 'bfloat16'")
         if dtype != self.dtype and self.engine is not None:
             self._weights.update(self.engine.get_weights())
-            acc = self.engine.accum.clone()
-            step = self.engine.step
+            slots = [s.clone() for s in self.engine.slots]
+            step, iterations = self.engine.step, self.engine.iterations
             self.engine = None
             self.dtype = dtype
             self._engine()
-            self.engine.accum.copy_(acc)
+            for dst, src in zip(self.engine.ensure_slots(len(slots)), slots):
+                dst.copy_(src)
             self.engine.step = step  # the default dropout seed continues (no repeated masks)
+            self.engine.iterations = iterations
         self.dtype = dtype
 
     def _engine(self):
@@ -199,16 +210,22 @@ class Model:
             pending = getattr(self, "_pending_accum", None)
             if pending is not None:
                 import torch
-                if isinstance(pending[0], str):  # ("named", {key: array}, step): per-tensor accumulators (Keras HDF5 optimizer_weights)
-                    for k, v in pending[1].items():
-                        off, shp = self.engine.pslices[k]
-                        self.engine.accum[off:off + int(np.prod(shp))].copy_(
-                            torch.as_tensor(np.ascontiguousarray(v, np.float32).reshape(-1)))
-                    self.engine.step = pending[2]
-                else:
-                    self.engine.accum.copy_(torch.as_tensor(pending[0]))
-                    self.engine.step = pending[1]
-                self._pending_accum = None
+                # slot 0 in _pending_accum, the optimizer's further slots (Adam's v) in the same
+                # form in _pending_slots
+                named = isinstance(pending[0], str)  # ("named", {key: array}, step): per-tensor state (Keras HDF5 optimizer_weights)
+                vals = [pending[1] if named else pending[0]] + list(getattr(self, "_pending_slots", None) or [])
+                for slot, val in zip(self.engine.ensure_slots(len(vals)), vals):
+                    if named:
+                        for k, v in val.items():
+                            off, shp = self.engine.pslices[k]
+                            slot[off:off + int(np.prod(shp))].copy_(
+                                torch.as_tensor(np.ascontiguousarray(v, np.float32).reshape(-1)))
+                    else:
+                        slot.copy_(torch.as_tensor(val))
+                self.engine.step = pending[2] if named else pending[1]
+                it = getattr(self, "_pending_iterations", None)  # (files from before `iterations`: the step)
+                self.engine.iterations = self.engine.step if it is None else int(it)
+                self._pending_accum = self._pending_slots = self._pending_iterations = None
             if self._dp_args is not None:  # re-wire DP into a rebuilt engine (dtype switch)
                 from . import dist as D
                 self._dp = D.attach(self.engine, *self._dp_args, broadcast=False)
@@ -294,7 +311,7 @@ class Model:
             kw = dict(sync=self._dp.finish, grad_scale=self._dp.grad_scale, seed=eng.step * w + r)
             if global_batch is not None:
                 kw["grad_frames"] = float(global_batch) / w
-        la = eng.train_step(self._to_dev(x), self._to_dev(y), lr=o.lr, rho=o.rho, eps=o.epsilon, **kw)
+        la = eng.train_step(self._to_dev(x), self._to_dev(y), optimizer=o, **kw)
         return la.cpu().numpy().tolist() if sync else la
 
     def _evaluate_means(self, x, y, batch_size):
@@ -486,17 +503,39 @@ class Model:
         return {"name": self.name, "layers": nodes, "input": self.inputs[0].layer.name,
                 "output": self.outputs[0].layer.name}
 
-    def named_accumulators(self):
-        """RMSprop accumulators per trainable weight (internal layout), or None before
-        the first step / without an optimizer state."""
+    def named_slots(self):
+        """The optimizer's state, one dict per slot (RMSprop: accumulators; SGD: moments;
+        Adam: m, v), each per trainable weight in the internal layout; or None before the
+        first step / without an optimizer state."""
         pending = getattr(self, "_pending_accum", None)
         if self.engine is None:
             if pending is not None and isinstance(pending[0], str):
-                return {k: v.copy() for k, v in pending[1].items()}
+                vals = [pending[1]] + list(getattr(self, "_pending_slots", None) or [])
+                return [{k: v.copy() for k, v in d.items()} for d in vals]
             return None
-        acc = self.engine.accum.cpu().numpy()
-        return {k: acc[off:off + int(np.prod(shp))].reshape(shp).copy()
-                for k, (off, shp) in self.engine.pslices.items()}
+        n = self.optimizer.slots if self.optimizer is not None else 1
+        out = []
+        for slot in self.engine.ensure_slots(n)[:n]:
+            a = slot.cpu().numpy()
+            out.append({k: a[off:off + int(np.prod(shp))].reshape(shp).copy()
+                        for k, (off, shp) in self.engine.pslices.items()})
+        return out
+
+    def named_accumulators(self):
+        """Slot 0 of named_slots() (RMSprop's accumulators), or None."""
+        slots = self.named_slots()
+        return None if slots is None else slots[0]
+
+    @property
+    def iterations(self):
+        """Updates applied so far (Keras' optimizer.iterations)."""
+        if self.engine is not None:
+            return self.engine.iterations
+        pending = getattr(self, "_pending_accum", None)
+        it = getattr(self, "_pending_iterations", None)
+        if it is None and pending is not None:
+            it = pending[2] if isinstance(pending[0], str) else pending[1]
+        return int(it or 0)
 
     @staticmethod
     def _is_h5_path(path):
@@ -505,7 +544,7 @@ class Model:
     def save(self, path, include_optimizer=True):
         """``*.h5`` / ``*.hdf5``: the Keras 2.2 HDF5 layout the reference's ModelCheckpoint
         writes (main.py:124; keras_h5.py).  Any other path: architecture + weights
-        (+ RMSprop accumulators) in one .npz."""
+        (+ the optimizer, its slots and counters, and the loss) in one .npz."""
         if self._is_h5_path(path):
             from . import keras_h5
             keras_h5.save_model_hdf5(self, path, include_optimizer=include_optimizer)
@@ -514,11 +553,17 @@ class Model:
         for k, v in self.named_weights().items():
             arrays["w/" + k] = v
         if include_optimizer and self.engine is not None:
-            arrays["opt/accum"] = self.engine.accum.cpu().numpy()
+            n = self.optimizer.slots if self.optimizer is not None else 1
+            for i, slot in enumerate(self.engine.ensure_slots(n)[:n]):  # slot 0 under its old name
+                arrays["opt/accum" if i == 0 else f"opt/slot{i}"] = slot.cpu().numpy()
             arrays["opt/step"] = np.array([self.engine.step])
+            arrays["opt/iterations"] = np.array([self.engine.iterations])
             arrays["opt/dtype"] = np.frombuffer(self.dtype.encode(), np.uint8)
         if self.optimizer is not None:
-            arrays["opt/hyper"] = np.array([self.optimizer.lr, self.optimizer.rho, self.optimizer.epsilon])
+            o = self.optimizer
+            cfg = {"class_name": o.class_name, "config": o.get_config(), "loss": self.loss,
+                   "metrics": [_METRIC_CONFIG[k] for k in self.metrics_names[1:]]}
+            arrays["opt/config"] = np.frombuffer(json.dumps(cfg).encode(), np.uint8)
         tmp = path + ".tmp.npz"
         np.savez(tmp, **arrays)
         os.replace(tmp, path)
@@ -592,11 +637,17 @@ def load_model(path, compile=True):
             built[c["name"]] = layer(ins if len(ins) > 1 else ins[0])
         m = Model(inputs=built[cfg["input"]], outputs=built[cfg["output"]], name=cfg["name"])
         m.set_named_weights({k[2:]: z[k] for k in z.files if k.startswith("w/")})
-        if compile and "opt/hyper" in z.files:
+        if compile and "opt/config" in z.files:
+            oc = json.loads(bytes(z["opt/config"]).decode())
+            m.compile(optimizers.from_config(oc["class_name"], oc["config"]), oc["loss"], oc["metrics"])
+        elif compile and "opt/hyper" in z.files:  # files from before the selectable optimizers
             lr, rho, eps = z["opt/hyper"].tolist()
             m.compile(RMSprop(lr=lr, rho=rho, epsilon=eps), "mse", ["accuracy"])
         if "opt/dtype" in z.files:
             m.dtype = bytes(z["opt/dtype"]).decode()
         if "opt/accum" in z.files:
             m._pending_accum = (z["opt/accum"].copy(), int(z["opt/step"][0]))
+            m._pending_slots = [z[k].copy() for k in sorted(f for f in z.files if f.startswith("opt/slot"))]
+            if "opt/iterations" in z.files:
+                m._pending_iterations = int(z["opt/iterations"][0])
     return m

@@ -359,6 +359,13 @@ def head_fwd_bwd_g3(dt, x: View, h_valid, wt, b, target, g3, part, aff=None, gra
          ptr(sh), ptr(target), ptr(g3), ptr(part), float(grad_numel), stream_ptr())
 
 
+def head_fwd_bwd_loss(loss, dt, x: View, h_valid, wt, b, target, part, dx=None, g3=None, aff=None, grad_numel=0.0):
+    """head_fwd_bwd (dx) or head_fwd_bwd_g3 (g3) with the loss `loss` (an L.LOSSES id)."""
+    sc, sh = aff if aff is not None else (None, None)
+    call("cnnitmo_head_fwd_bwd_loss", loss, dt, x.ptr, x.n, x.h, h_valid, x.w, x.c, ptr(wt), ptr(b), ptr(sc),
+         ptr(sh), ptr(target), ptr(dx), ptr(g3), ptr(part), float(grad_numel), stream_ptr())
+
+
 def bn_bwd_apply_g3(dt, g3, wh, r, c, p, coef, dz, part):
     rp, rld, roff = _rview(r, c)
     call("cnnitmo_bn_bwd_apply_g3", dt, ptr(g3), ptr(wh), rp, rld, roff, p, c, ptr(coef), ptr(dz), ptr(part),
@@ -399,6 +406,17 @@ def pool_bnsums_pooled(dt, dyp, pr, n, h, w, c, mean, inv, part):
 
 def rmsprop(p, g, a, lr, rho, eps, grad_scale=1.0):
     call("cnnitmo_rmsprop", ptr(p), ptr(g), ptr(a), p.numel(), lr, rho, eps, grad_scale, stream_ptr())
+
+
+def adam(p, g, m, v, lr_t, beta1, beta2, eps, grad_scale=1.0):
+    """lr_t: the bias-corrected rate lr*sqrt(1-beta2^t)/(1-beta1^t) (see cnn_itmo.h)."""
+    call("cnnitmo_adam", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr_t, beta1, beta2, eps, grad_scale,
+         stream_ptr())
+
+
+def sgd(p, g, mom, lr, momentum=0.0, nesterov=False, grad_scale=1.0):
+    call("cnnitmo_sgd", ptr(p), ptr(g), ptr(mom), p.numel(), lr, momentum, int(bool(nesterov)), grad_scale,
+         stream_ptr())
 
 
 def augment_affine(src, mats, flips, scale, dst):

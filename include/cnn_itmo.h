@@ -432,6 +432,31 @@ int cnnitmo_head_finalize(const float* part, long rows, int cin, double numel,
 /* scale/shift (nullable, [cin]): x holds r and the head's input is r*scale +
  * shift (folded BN); dx is then d/dy and dw the gradient w.r.t. the raw W. */
 
+/* The training loss as a parameter: the mean over n*h_valid*w*3 elements of the term l,
+ * with y = sigmoid(z), t the target, evaluated in fp32:
+ *   CNNITMO_LOSS_MSE      l = (y-t)^2                                dl/dz = 2(y-t) y(1-y)
+ *   CNNITMO_LOSS_MAE      l = |y-t|                                  sign(y-t) y(1-y), sign(0) = 0
+ *   CNNITMO_LOSS_LOGCOSH  l = |x| + log1p(exp(-2|x|)) - ln 2, x=y-t  tanh(x) y(1-y)
+ *                         (= ln cosh x; Keras' x + softplus(-2x) - ln 2)
+ *   CNNITMO_LOSS_MSLE     l = (a-b)^2, a = ln(max(y,1e-7)+1),        2(a-b)/(y+1) y(1-y) for y >= 1e-7,
+ *                         b = ln(max(t,1e-7)+1)                      else 0
+ *   CNNITMO_LOSS_BCE      l = max(z,0) - z t + log1p(exp(-|z|))      y - t
+ * BCE is computed from the logit z itself.  Keras clips y to [1e-7, 1-1e-7] and converts it
+ * back to a logit first; the two agree for |z| < 16.1 and differ beyond (no clipping here).
+ * Exactly one of dx (as cnnitmo_head_fwd_bwd) and g3 (as cnnitmo_head_fwd_bwd_g3) is non-null;
+ * an unknown loss or a bad dx/g3 pair is CNNITMO_EINVAL before any launch.  'accuracy', db, dW,
+ * the part layout and cnnitmo_head_finalize are the same for every loss;
+ * cnnitmo_head_fwd_bwd[_g3] are this call with CNNITMO_LOSS_MSE. */
+#define CNNITMO_LOSS_MSE 0
+#define CNNITMO_LOSS_MAE 1
+#define CNNITMO_LOSS_LOGCOSH 2
+#define CNNITMO_LOSS_MSLE 3
+#define CNNITMO_LOSS_BCE 4
+int cnnitmo_head_fwd_bwd_loss(int loss, int dtype, const void* x, int n, int h, int h_valid, int w, int cin,
+                              const float* wt, const float* b, const float* scale, const float* shift,
+                              const float* target, void* dx /*nullable*/, float* g3 /*nullable*/,
+                              float* part, double grad_numel, void* stream);
+
 /* ---------------------------------------------------------------------------
  * RMSprop (keras.optimizers.RMSprop defaults via compile('rmsprop'), model.py:281):
  *   a <- rho*a + (1-rho)*g'^2 ; p <- p - lr*g'/(sqrt(a)+eps),  g' = g*grad_scale
@@ -439,6 +464,18 @@ int cnnitmo_head_finalize(const float* part, long rows, int cin, double numel,
  */
 int cnnitmo_rmsprop(float* p, const float* g, float* a, long n, float lr, float rho, float eps,
                     float grad_scale, void* stream);
+/* Adam and SGD with Keras 2.2's arithmetic, over the same flat buffers (16-byte aligned,
+ * g' = g*grad_scale):
+ *   Adam: m <- beta1*m + (1-beta1)*g' ; v <- beta2*v + (1-beta2)*g'^2 ;
+ *         p <- p - lr_t*m/(sqrt(v)+eps), the caller passing the bias-corrected
+ *         lr_t = lr*sqrt(1-beta2^t)/(1-beta1^t), t = applied updates so far + 1 (no amsgrad);
+ *   SGD:  mom <- momentum*mom - lr*g' ; p <- p + mom, or with nesterov != 0
+ *         p <- p + momentum*mom - lr*g'.
+ * A `decay` is the caller's: lr/(1 + decay*iterations) before the call. */
+int cnnitmo_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, float beta1, float beta2,
+                 float eps, float grad_scale, void* stream);
+int cnnitmo_sgd(float* p, const float* g, float* mom, long n, float lr, float momentum, int nesterov,
+                float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Training-data augmentation -- replaces the paired keras ImageDataGenerator
