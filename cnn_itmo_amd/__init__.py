@@ -10,9 +10,9 @@ from .model import Model, load_model
 from .optimizers import SGD, Adam, RMSprop
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import CSVLogger, LambdaCallback, ModelCheckpoint
-from . import metrics
+from . import hdrio, metrics
 
 __all__ = ["Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
            "Adam", "SGD", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
-           "LambdaCallback", "ModelCheckpoint", "metrics"]
+           "LambdaCallback", "ModelCheckpoint", "metrics", "hdrio"]

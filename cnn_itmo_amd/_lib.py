@@ -123,6 +123,8 @@ SIGNATURES = {
                                         vp]),
     "cnnitmo_adam": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),
+    "cnnitmo_rgbe_encode": (i32, [vp, i64, vp, vp]),
+    "cnnitmo_rgbe_decode": (i32, [vp, i64, vp, vp]),
 }
 
 

@@ -451,3 +451,24 @@ def image_metrics(what, a, b, max_val=1.0, out=None):
     call("cnnitmo_image_metrics", what, ptr(a), ptr(b), n, h, w, float(max_val), ptr(out), ws.data_ptr(),
          ws.numel(), stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------- RGBE codec
+def _rgbe_pair(rgb, rgbe):
+    assert rgb.dtype == torch.float32 and rgbe.dtype == torch.uint8 and rgb.is_contiguous() and rgbe.is_contiguous()
+    assert rgb.shape[-1] == 3 and rgbe.shape[-1] == 4 and rgb.shape[:-1] == rgbe.shape[:-1], \
+        (tuple(rgb.shape), tuple(rgbe.shape))
+    return rgb.numel() // 3
+
+
+def rgbe_encode(rgb, rgbe):
+    """rgb [...,3] fp32 -> rgbe [...,4] uint8, contiguous device tensors (cnnitmo_rgbe_encode).  Views
+    that do not start on a 16-byte boundary take the kernel's one-pixel path: same bytes."""
+    call("cnnitmo_rgbe_encode", ptr(rgb), _rgbe_pair(rgb, rgbe), ptr(rgbe), stream_ptr())
+    return rgbe
+
+
+def rgbe_decode(rgbe, rgb):
+    """rgbe [...,4] uint8 -> rgb [...,3] fp32, contiguous device tensors (cnnitmo_rgbe_decode)."""
+    call("cnnitmo_rgbe_decode", ptr(rgbe), _rgbe_pair(rgb, rgbe), ptr(rgb), stream_ptr())
+    return rgb

@@ -11,7 +11,8 @@ Here the same conventions run batched on the GPU:
     python -m cnn_itmo_amd.predict --model saved7-model-218-0.73.hdf5 \\
         [--input images_to_predict/input] [--output images_to_predict/output] \\
         [--batch 8] [--dtype float32|bfloat16] [--tile TH,TW] \\
-        [--reference ground_truth_dir [--metrics-csv scores.csv]]
+        [--reference ground_truth_dir [--metrics-csv scores.csv]] \\
+        [--hdr DIR [--hdr-format hdr|pfm] [--hdr-mode script|exact] [--hdr-key A] [--hdr-log-average G]]
 
 Differences, all deliberate: images are processed in sorted order, in batches
 of equal-sized frames; the output file name is the input's base name (the
@@ -78,11 +79,14 @@ def _pad_cols(x, W):
     return out
 
 
-def predict_frames(model, frames_u8, batch=8, cache=None, tile=None):
+def predict_frames(model, frames_u8, batch=8, cache=None, tile=None, return_float=False):
     """uint8 frames (equal sizes) -> uint8 predictions, reference conventions.
     ``tile`` (th, tw): spatially tiled inference with 96-px halos (tiled.py; same
-    result, activation memory bounded by the window instead of the frame)."""
+    result, activation memory bounded by the window instead of the frame).
+    ``return_float``: return (uint8 predictions, float32 predictions) -- the model's output
+    before the 8-bit truncation, for the HDR reconstruction of ``--hdr-mode exact``."""
     h, w = frames_u8[0].shape[:2]
+    floats = []
     if tile is not None:
         from .tiled import predict_tiled
         outs = []
@@ -90,7 +94,9 @@ def predict_frames(model, frames_u8, batch=8, cache=None, tile=None):
             x = np.stack([to_input(f) for f in frames_u8[i:i + batch]])
             y = predict_tiled(model, x, tile, batch_size=batch, cache=cache)
             outs.extend(to_png(y[j]) for j in range(y.shape[0]))
-        return outs
+            if return_float:
+                floats.extend(y[j] for j in range(y.shape[0]))
+        return (outs, floats) if return_float else outs
     m = model_for_size(model, h, w, cache)
     W = m.inputs[0].shape[1]
     outs = []
@@ -98,7 +104,9 @@ def predict_frames(model, frames_u8, batch=8, cache=None, tile=None):
         x = np.stack([to_input(f) for f in frames_u8[i:i + batch]])
         y = m.predict(_pad_cols(x, W), batch_size=batch)
         outs.extend(to_png(y[j, :h, :w]) for j in range(y.shape[0]))
-    return outs
+        if return_float:
+            floats.extend(y[j, :h, :w] for j in range(y.shape[0]))
+    return (outs, floats) if return_float else outs
 
 
 def score_png(pred_u8, ref_path):
@@ -113,17 +121,44 @@ def score_png(pred_u8, ref_path):
     return float(ps.item()), float(ss.item())
 
 
+def write_hdr_prediction(path, pred_u8, pred_f32=None, mode="script", key=0.18, log_average=1.0):
+    """The HDR reconstruction of one prediction as ``path`` (.hdr or .pfm).  ``script``:
+    inverse_Reinhard.m on the written 8-bit prediction; ``exact``: the algebraic inverse of
+    Reinhard.m on the float prediction for the HDR log-average ``log_average``.  The inverse map
+    and the RGBE encode run on the GPU; a .hdr leaves the device as 4 bytes per pixel."""
+    from . import hdrio, tonemap
+    if mode == "script":
+        hdr = tonemap.inverse_reinhard(np.ascontiguousarray(pred_u8), a=key, mode="script")
+    elif mode == "exact":
+        hdr = tonemap.inverse_reinhard(np.ascontiguousarray(pred_f32), a=key, g=log_average, mode="exact")
+    else:
+        raise ValueError(f"hdr mode {mode!r} (script or exact)")
+    hdrio.write_image(path, hdr[0])
+
+
 def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None, reference=None,
-                metrics_csv=None):
+                metrics_csv=None, hdr_dir=None, hdr_format="hdr", hdr_mode="script", hdr_key=0.18,
+                hdr_log_average=1.0):
     """``reference``: a directory of ground-truth PNGs; every written prediction is scored
     against the file of the same name there (PSNR / SSIM, logged per file and as the mean; a
     missing reference is reported and skipped, a size mismatch raises).  ``metrics_csv``:
-    also write ``name;psnr;ssim`` rows to that file."""
+    also write ``name;psnr;ssim`` rows to that file.
+    ``hdr_dir``: also write every prediction's HDR reconstruction there as ``name.hdr`` (Radiance
+    RGBE) or ``name.pfm`` (``hdr_format``); ``hdr_mode`` 'script' applies inverse_Reinhard.m to
+    the written 8-bit prediction, 'exact' the exact inverse of Reinhard.m (key ``hdr_key``,
+    log-average ``hdr_log_average``) to the float prediction.  The PNGs are the same either way."""
     from PIL import Image
+    if hdr_format not in ("hdr", "pfm"):
+        raise ValueError(f"hdr format {hdr_format!r} (hdr or pfm)")
+    if hdr_mode not in ("script", "exact"):
+        raise ValueError(f"hdr mode {hdr_mode!r} (script or exact)")
     files = sorted(glob.glob(os.path.join(in_dir, pattern)))
     if not files:
         raise FileNotFoundError(f"no {pattern} files in {in_dir}")
     os.makedirs(out_dir, exist_ok=True)
+    if hdr_dir is not None:
+        os.makedirs(hdr_dir, exist_ok=True)
+    want_float = hdr_dir is not None and hdr_mode == "exact"
     groups = {}
     frames = {f: read_png(f) for f in files}
     for f in files:
@@ -133,11 +168,16 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
     scores = []
     for shape, fs in groups.items():
         log(f"Grabbing {len(fs)} input files of {shape[1]}x{shape[0]}")
-        preds = predict_frames(model, [frames[f] for f in fs], batch, cache, tile)
-        for f, p in zip(fs, preds):
+        preds = predict_frames(model, [frames[f] for f in fs], batch, cache, tile, return_float=want_float)
+        preds, floats = preds if want_float else (preds, [None] * len(fs))
+        for f, p, pf in zip(fs, preds, floats):
             dst = os.path.join(out_dir, os.path.basename(f))
             Image.fromarray(p).save(dst)
             written.append(dst)
+            if hdr_dir is not None:
+                stem = os.path.splitext(os.path.basename(f))[0]
+                write_hdr_prediction(os.path.join(hdr_dir, f"{stem}.{hdr_format}"), p, pf, hdr_mode, hdr_key,
+                                     hdr_log_average)
             if reference is not None:
                 ref = os.path.join(reference, os.path.basename(f))
                 if not os.path.exists(ref):
@@ -170,6 +210,16 @@ def main(argv=None):
                     help="directory of ground-truth PNGs: score each written PNG against the same-named file "
                          "(PSNR and SSIM of the 8-bit images)")
     ap.add_argument("--metrics-csv", default=None, help="with --reference: write name;psnr;ssim rows to this file")
+    ap.add_argument("--hdr", default=None, metavar="DIR",
+                    help="also write each prediction's HDR reconstruction (inverse Reinhard) to DIR/name.hdr")
+    ap.add_argument("--hdr-format", default="hdr", choices=["hdr", "pfm"],
+                    help="Radiance RGBE (.hdr) or lossless PFM (.pfm)")
+    ap.add_argument("--hdr-mode", default="script", choices=["script", "exact"],
+                    help="script: inverse_Reinhard.m on the written 8-bit PNG; exact: the exact inverse of "
+                         "Reinhard.m on the float prediction (no banding)")
+    ap.add_argument("--hdr-key", type=float, default=0.18, help="the Reinhard key a")
+    ap.add_argument("--hdr-log-average", type=float, default=1.0,
+                    help="exact mode: the log-average luminance of the HDR image to reconstruct")
     a = ap.parse_args(argv)
     if a.metrics_csv and not a.reference:
         ap.error("--metrics-csv needs --reference")
@@ -179,8 +229,12 @@ def main(argv=None):
     if m.optimizer is None:
         m.compile(optimizer="rmsprop", loss="mse", metrics=["accuracy"])
     m.set_dtype(a.dtype)
-    out = predict_dir(m, a.input, a.output, a.batch, tile=tile, reference=a.reference, metrics_csv=a.metrics_csv)
+    out = predict_dir(m, a.input, a.output, a.batch, tile=tile, reference=a.reference, metrics_csv=a.metrics_csv,
+                      hdr_dir=a.hdr, hdr_format=a.hdr_format, hdr_mode=a.hdr_mode, hdr_key=a.hdr_key,
+                      hdr_log_average=a.hdr_log_average)
     print(f"wrote {len(out)} predictions to {a.output}")
+    if a.hdr:
+        print(f"wrote {len(out)} .{a.hdr_format} reconstructions to {a.hdr}")
     return 0
 
 

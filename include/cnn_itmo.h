@@ -57,7 +57,8 @@ extern "C" {
 
 /* ABI version: 2 since CNNITMO_CONSUMER_ROWS went from 16 to 64 (a caller built against the
  * old header under-allocates cnnitmo_bn_consumer_sums' part: check cnnitmo_consumer_rows()) and
- * cnnitmo_bn_apply started to require 16-byte aligned scale / shift. */
+ * cnnitmo_bn_apply started to require 16-byte aligned scale / shift.  Added since without a bump
+ * (new entry points only, nothing existing changed): cnnitmo_rgbe_encode / cnnitmo_rgbe_decode. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -533,6 +534,24 @@ int cnnitmo_inverse_reinhard_apply(int mode, const void* sdr, int n, int h, int 
 long cnnitmo_image_metrics_workspace_bytes(int n, int h, int w);
 int cnnitmo_image_metrics(int what, const float* a, const float* b, int n, int h, int w, double max_val,
                           double* out, void* workspace, long workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Radiance RGBE (.hdr / .pic) pixel codec: [npix][3] fp32 <-> [npix][4] bytes
+ * (red, green, blue mantissas, shared exponent), device pointers.
+ *   encode: NaN -> 0, components clamped to [0, 255 * 2^119]; v = max(r, g, b);
+ *           v < 1e-32f -> (0,0,0,0); else frexpf(v) = (m, e), mantissa =
+ *           floor(ldexpf(c, 8 - e)) (truncation; the largest is in 128..255),
+ *           exponent byte = e + 128.
+ *   decode: exponent byte 0 -> (0,0,0) whatever the mantissas; else
+ *           c = (float)mantissa * 2^(E - 136), no +0.5 (rgbe.c, MATLAB hdrread).
+ *           Every result is exact in fp32; E = 1 gives denormals, not flushed.
+ * rgb must be 4-byte aligned.  16-byte accesses (four pixels per thread) when
+ * both pointers are 16-byte aligned, one pixel per thread otherwise and for the
+ * npix % 4 tail; the bytes are the same either way.  A null pointer or
+ * npix <= 0 is CNNITMO_EINVAL before any device call.
+ */
+int cnnitmo_rgbe_encode(const float* rgb, long npix, uint8_t* rgbe, void* stream);
+int cnnitmo_rgbe_decode(const uint8_t* rgbe, long npix, float* rgb, void* stream);
 
 #ifdef __cplusplus
 }
