@@ -391,7 +391,7 @@ class LaunchChecker(ElementwiseChecks):
         lab = f"conv_c3_fwd {n}x{h}x{w} (valid {hv})"
         acc, ot = _Acc(self, lab, dt), out.tensor()
         s1 = torch.zeros(32, dtype=F64, device=x.device)
-        sa = torch.zeros_like(s1)
+        s2, sa = torch.zeros_like(s1), torch.zeros_like(s1)
         for i in range(n):
             z = _epilogue(_conv3(xin[i], W) + bias.to(F64), flags, aff)
             sl = _f32_slack(dt, 27, _conv3(xin[i].abs(), W.abs()))
@@ -399,11 +399,13 @@ class LaunchChecker(ElementwiseChecks):
                 sl = sl * aff[0].to(F64).abs()
             acc.add(ot[i], z, sl)
             s1 += z.sum((0, 1))
+            s2 += (z * z).sum((0, 1))
             sa += z.abs().sum((0, 1))
         acc.done()
         if stats is not None and flags & L.STATS:
             tot = stats.view(-1, 2, 32).to(F64).sum(0)
             self._sums(lab + " stats", tot[0], s1, sa)
+            self._sums(lab + " stats^2", tot[1], s2, s2)
 
     def _chk_conv_c3_wgrad(self, dt, x, n, hv, h, w, dz, dw):
         xin = self._c3_input(x, n, hv, h, w, dt)

@@ -39,6 +39,11 @@ def host(t):
     return t.float().cpu().numpy().astype(np.float64)
 
 
+def nans(shape, dtype=torch.float32):
+    """A kernel output whose every element the contract says is written: handed over as NaN."""
+    return torch.full(shape if isinstance(shape, tuple) else (shape,), float("nan"), dtype=dtype, device="cuda")
+
+
 def close(got, want, dt, what=""):
     scale = max(1.0, float(np.abs(want).max()))
     err = float(np.abs(got - want).max())
@@ -74,21 +79,22 @@ def test_conv3x3_fwd_dgrad_wgrad(dt, cin, cout, H, W):
     ops.prep_conv3x3(d, torch.tensor(w).cuda(), cout, cin, wf, wflip)
     out = ops.new_view(N, H, W, cout, TDT[dt])
     rows = ops.conv3x3_stat_rows(d, N, H, W, cin, cout)
-    stats = torch.zeros(rows, 2, cout, device="cuda")
+    stats = nans((rows, 2, cout))
     ops.conv3x3_fwd(d, xv, wf, torch.tensor(b).cuda(), out, flags=1 | 2, stats=stats)
     torch.cuda.synchronize()
     close(host(out.buf).reshape(N, H, W, cout), r_ref, dt, "fwd")
     s = stats.sum(0).double().cpu().numpy()
     close(s[0] / r_ref.size * cout, r_ref.reshape(-1, cout).mean(0), dt, "stat sum")
+    close(s[1] / r_ref.size * cout, (r_ref ** 2).reshape(-1, cout).mean(0), dt, "stat sum of squares")
     # dgrad into a view of a wider buffer
     dz = rng.standard_normal((N, H, W, cout)).astype(np.float32)
     dzr = rnd(dz, dt)
     dx_ref, dw_ref, db_ref = R.conv2d_same_bwd(x, wr, dzr)
-    dxb = torch.zeros(N * H * W * ld, dtype=TDT[dt], device="cuda")
+    dxb = nans(N * H * W * ld, TDT[dt])
     ops.conv3x3_dgrad(d, dev(dz, dt), N, H, W, cout, wflip, cin, ops.View(dxb, N, H, W, cin, ld, off))
     torch.cuda.synchronize()
     close(host(dxb).reshape(N, H, W, ld)[..., off:], dx_ref, dt, "dgrad")
-    assert float(host(dxb).reshape(N, H, W, ld)[..., :off].max()) == 0.0  # other slice untouched
+    assert np.isnan(host(dxb).reshape(N, H, W, ld)[..., :off]).all()  # other slice untouched
     dw = torch.empty(cout, 3, 3, cin, device="cuda")
     ops.conv_wgrad(d, 9, xv, dev(dz, dt), cout, dw)
     torch.cuda.synchronize()
@@ -166,17 +172,19 @@ def test_tconv(dt, cin, cout, H, W):
     ops.prep_tconv(d, torch.tensor(k).cuda(), cout, cin, kf, kT)
     # output into a concat slice: ld = cout + 64, off = 64
     ld = cout + 64
-    ob = torch.zeros(N * 2 * H * 2 * W * ld, dtype=TDT[dt], device="cuda")
+    ob = nans(N * 2 * H * 2 * W * ld, TDT[dt])
     rows = ops.tconv_stat_rows(d, N, H, W, cin, cout)
-    stats = torch.zeros(rows, 2, 4 * cout, device="cuda")
+    stats = nans((rows, 2, 4 * cout))
     xv = ops.View(dev(x, dt).reshape(-1), N, H, W, cin, cin)
     ops.tconv_fwd(d, xv, kf, torch.tensor(b).cuda(), ops.View(ob, N, 2 * H, 2 * W, cout, ld, 64),
                   flags=1 | 2, stats=stats)
     torch.cuda.synchronize()
     got = host(ob).reshape(N, 2 * H, 2 * W, ld)
     close(got[..., 64:], ref, dt, "tconv fwd")
-    s = stats.sum(0).double().cpu().numpy()[0].reshape(4, cout).sum(0)
-    close(s / (ref.size / cout), ref.reshape(-1, cout).mean(0), dt, "tconv stats")
+    assert np.isnan(got[..., :64]).all()  # the other concat member untouched
+    s = stats.sum(0).double().cpu().numpy().reshape(2, 4, cout).sum(1)
+    close(s[0] / (ref.size / cout), ref.reshape(-1, cout).mean(0), dt, "tconv stats")
+    close(s[1] / (ref.size / cout), (ref ** 2).reshape(-1, cout).mean(0), dt, "tconv stats, sum of squares")
     dout = rng.standard_normal((N, 2 * H, 2 * W, cout)).astype(np.float32)
     dx_ref, dk_ref, _ = R.tconv2x2s2_bwd(xr, kr, rnd(dout, dt))
     dx = torch.empty(N * H * W * cin, dtype=TDT[dt], device="cuda")
@@ -207,7 +215,7 @@ def test_tconv_affine_inference_epilogue(dt, cin, cout, H, W):
     kf = torch.empty(k.size, dtype=TDT[dt], device="cuda")
     kT = torch.empty(k.size, dtype=TDT[dt], device="cuda")
     ops.prep_tconv(d, torch.tensor(k).cuda(), cout, cin, kf, kT)
-    out = torch.zeros(N * 2 * H * 2 * W * cout, dtype=TDT[dt], device="cuda")
+    out = nans(N * 2 * H * 2 * W * cout, TDT[dt])
     ops.tconv_fwd(d, ops.View(dev(x, dt).reshape(-1), N, H, W, cin, cin), kf, torch.tensor(b).cuda(),
                   ops.View(out, N, 2 * H, 2 * W, cout, cout, 0), flags=1 | 4,
                   aff=(torch.tensor(sc).cuda(), torch.tensor(sh).cuda()))
@@ -278,10 +286,10 @@ def test_first_layer_direct(N, Hv, H, W, ld, off, dt):
     b = rng.standard_normal(32).astype(np.float32)
     wp = torch.empty(32 * 32, dtype=TDT[dt], device="cuda")
     ops.prep_c3(DT[dt], torch.tensor(w).cuda(), 32, wp)
-    buf = torch.zeros(N * H * W * ld, dtype=TDT[dt], device="cuda")
+    buf = nans(N * H * W * ld, TDT[dt])
     out = ops.View(buf, N, H, W, 32, ld, off)
     rows = ops.conv_c3_stat_rows(N, H, W)
-    stats = torch.empty(rows * 64, device="cuda")
+    stats = nans(rows * 64)
     xd = torch.tensor(x).cuda()
     ops.conv_c3_fwd(DT[dt], xd, N, Hv, H, W, wp, torch.tensor(b).cuda(), out, flags=1 | 2, stats=stats)
     xp = np.zeros((N, H, W, 3))
@@ -347,7 +355,7 @@ def test_bn_train_fwd_bwd(dt, drop, C):
     sc, sh, sm, si = (torch.empty(C, device="cuda") for _ in range(4))
     ops.bn_fwd_finalize(stats, 1, C, 1, P, cu(g), cu(be), mm, mv, 0.99, 1e-3, sc, sh, sm, si)
     ld, off = C + 32, 32
-    yb = torch.zeros(P * ld, dtype=TDT[dt], device="cuda")
+    yb = nans(P * ld, TDT[dt])
     seed, layer = 123, 1
     ops.bn_apply(d, rt, P, C, sc, sh, ops.View(yb, N, H, W, C, ld, off), flags=1 if drop else 0,
                  seed=seed, layer=layer)
@@ -470,14 +478,14 @@ def test_conv3x3_fwd_pool(dt, cin, cout, H, W):
     bias = torch.tensor(b).cuda()
     ref = ops.new_view(N, H, W, cout, T)
     rows = ops.conv3x3_stat_rows(d, N, H, W, cin, cout)
-    st0 = torch.zeros(rows * 2 * cout, device="cuda")
+    st0 = nans(rows * 2 * cout)
     ops.conv3x3_fwd(d, xv, wf, bias, ref, 1 | 2, stats=st0)
     sign = torch.tensor(np.resize([1.0, -0.5, 0.0, 3.0], cout).astype(np.float32)).cuda()
     for sg in (sign, None):
         out = ops.new_view(N, H, W, cout, T)
         pv = torch.empty(N * (H // 2) * (W // 2) * cout, dtype=T, device="cuda")
         pi = torch.empty(N * (H // 2) * (W // 2) * cout, dtype=torch.uint8, device="cuda")
-        st = torch.zeros(rows * 2 * cout, device="cuda")
+        st = nans(rows * 2 * cout)
         ops.conv3x3_fwd_pool(d, xv, wf, bias, out, pv, pi, sg, flags=1 | 2, stats=st)
         torch.cuda.synchronize()
         assert torch.equal(out.buf, ref.buf)
@@ -559,7 +567,7 @@ def test_conv3x3_fwd_cat_dec9(H, W):
     v2 = ops.View(dev(x2, "bf16").reshape(-1), N, H, W, 64, 64)
     out = ops.new_view(N, H, W, 64, torch.bfloat16)
     rows = ops.conv3x3_stat_rows(1, N, H, W, 96, 64)
-    st = torch.zeros(rows * 128, device="cuda")
+    st = nans(rows * 128)
     ops.conv3x3_fwd_cat(1, v1, v2, wf, torch.tensor(b).cuda(), out, 1 | 2, stats=st)
     torch.cuda.synchronize()
     xc = np.concatenate([rnd(x1, "bf16"), rnd(x2, "bf16")], 3).astype(np.float64)
