@@ -8,11 +8,12 @@ from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2D
                      Input, InputLayer, MaxPooling2D, clear_session, concatenate)
 from .model import Model, load_model
 from .optimizers import SGD, Adam, RMSprop
+from .losses import DSSIM
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import CSVLogger, LambdaCallback, ModelCheckpoint
 from . import hdrio, metrics
 
 __all__ = ["Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
-           "Adam", "SGD", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
+           "Adam", "SGD", "DSSIM", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
            "LambdaCallback", "ModelCheckpoint", "metrics", "hdrio"]

@@ -24,6 +24,9 @@ BIAS_PER_COL = 8
 CONSUMER_ROWS = 64
 # CNNITMO_LOSS_*: canonical loss name -> id
 LOSSES = {"mse": 0, "mae": 1, "logcosh": 2, "msle": 3, "binary_crossentropy": 4}
+LOSS_GIVEN = 5  # the head with its output gradient given (cnnitmo_head_fwd_bwd_given)
+# CNNITMO_BASE_*: the DSSIM loss's pointwise base term -> id
+DSSIM_BASES = {None: 0, "mae": 1, "mse": 2}
 
 vp = C.c_void_p
 i32 = C.c_int
@@ -121,6 +124,10 @@ SIGNATURES = {
     "cnnitmo_rmsprop": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp]),
     "cnnitmo_head_fwd_bwd_loss": (i32, [i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64,
                                         vp]),
+    "cnnitmo_head_fwd_bwd_given": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "cnnitmo_dssim_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "cnnitmo_dssim_loss_grad": (i32, [i32, f64, vp, vp, i32, i32, i32, f64, vp, vp, vp, i64, vp]),
+    "cnnitmo_rgb_accuracy": (i32, [vp, vp, i64, vp, vp]),
     "cnnitmo_adam": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),
     "cnnitmo_rgbe_encode": (i32, [vp, i64, vp, vp]),

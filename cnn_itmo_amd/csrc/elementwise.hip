@@ -787,8 +787,9 @@ extern "C" int cnnitmo_head_rows(long p) {
 // The training loss of one output element (cnn_itmo.h, CNNITMO_LOSS_*): its term l and
 // g = dl/dz, z the head's logit, y = sigmoid(z), t the target; fp32, without the 1/numel
 // of the mean.  Both head kernels call this and nothing else differs between the losses.
+// CNNITMO_LOSS_GIVEN: dyv = dL/dy comes from outside, already normalised; no term of its own.
 template <int LOSS>
-__device__ __forceinline__ void loss_term(float z, float y, float t, float& l, float& g) {
+__device__ __forceinline__ void loss_term(float z, float y, float t, float& l, float& g, float dyv = 0.f) {
   if constexpr (LOSS == CNNITMO_LOSS_MSE) {
     const float e = y - t;
     l = e * e;
@@ -806,6 +807,9 @@ __device__ __forceinline__ void loss_term(float z, float y, float t, float& l, f
     const float a = logf(fmaxf(y, 1e-7f) + 1.f), b = logf(fmaxf(t, 1e-7f) + 1.f);
     l = (a - b) * (a - b);
     g = y >= 1e-7f ? 2.f * (a - b) / (y + 1.f) * y * (1.f - y) : 0.f;
+  } else if constexpr (LOSS == CNNITMO_LOSS_GIVEN) {
+    l = 0.f;
+    g = dyv * (y * (1.f - y));
   } else {
     // binary cross-entropy on the unclipped logit (Keras clips y to [1e-7, 1-1e-7] first)
     static_assert(LOSS == CNNITMO_LOSS_BCE, "unknown loss");
@@ -852,7 +856,7 @@ __global__ void head_kernel(const T* __restrict__ x, int N, int H, int Hv, int W
   // HEAD_U pixel slots per lane group per iteration, all their loads issued first:
   // one 16-byte load in flight per lane left this HBM pass at ~2 TB/s
   for (long base0 = (long)blockIdx.x * ppb * HEAD_U; base0 < P; base0 += (long)gridDim.x * ppb * HEAD_U) {
-    float v[HEAD_U][VE], tg[HEAD_U][3];
+    float v[HEAD_U][VE], tg[HEAD_U][3], gv[HEAD_U][3];  // gv: the given dy (CNNITMO_LOSS_GIVEN; yhat holds it)
     bool inb[HEAD_U], valid[HEAD_U];
     size_t tix[HEAD_U];
 #pragma unroll
@@ -883,6 +887,12 @@ __global__ void head_kernel(const T* __restrict__ x, int N, int H, int Hv, int W
 #pragma unroll
         for (int o = 0; o < 3; ++o) tg[u][o] = valid[u] ? target[tix[u] + o] : 0.f;
       }
+#pragma unroll
+      for (int o = 0; o < 3; ++o) gv[u][o] = 0.f;
+      if constexpr (BWD && LOSS == CNNITMO_LOSS_GIVEN) {
+#pragma unroll
+        for (int o = 0; o < 3; ++o) gv[u][o] = valid[u] ? yhat[tix[u] + o] : 0.f;
+      }
     }
 #pragma unroll
     for (int u = 0; u < HEAD_U; ++u) {
@@ -912,9 +922,9 @@ __global__ void head_kernel(const T* __restrict__ x, int N, int H, int Hv, int W
       if (valid[u]) {
         const float t0 = tg[u][0], t1 = tg[u][1], t2 = tg[u][2];
         float l0, l1, l2, g0, g1, g2;
-        loss_term<LOSS>(z[0], yh[0], t0, l0, g0);
-        loss_term<LOSS>(z[1], yh[1], t1, l1, g1);
-        loss_term<LOSS>(z[2], yh[2], t2, l2, g2);
+        loss_term<LOSS>(z[0], yh[0], t0, l0, g0, gv[u][0]);
+        loss_term<LOSS>(z[1], yh[1], t1, l1, g1, gv[u][1]);
+        loss_term<LOSS>(z[2], yh[2], t2, l2, g2, gv[u][2]);
         if (sub == 0) {
           lsum += l0 + l1 + l2;
           const int at = (t1 > t0) ? ((t2 > t1) ? 2 : 1) : ((t2 > t0) ? 2 : 0);
@@ -1077,6 +1087,14 @@ __global__ __launch_bounds__(256) void head2_kernel(const T* __restrict__ x, int
     const bool valid = inb && h < Hv;
     const size_t tix = (((size_t)n * Hv + h) * W + wc) * 3;
     const float t0 = tv[0], t1 = tv[1], t2 = tv[2];
+    float gv0 = 0.f, gv1 = 0.f, gv2 = 0.f;  // the given dy (CNNITMO_LOSS_GIVEN; yhat holds it)
+    if constexpr (BWD && LOSS == CNNITMO_LOSS_GIVEN) {
+      if (valid) {
+        gv0 = yhat[tix];
+        gv1 = yhat[tix + 1];
+        gv2 = yhat[tix + 2];
+      }
+    }
 #pragma unroll
     for (int u = 0; u < LPP; ++u) {
       float v[VE];
@@ -1110,9 +1128,9 @@ __global__ __launch_bounds__(256) void head2_kernel(const T* __restrict__ x, int
     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
     if (valid) {
       float l0, l1, l2, g0, g1, g2;
-      loss_term<LOSS>(z.x + b0, y0, t0, l0, g0);
-      loss_term<LOSS>(z.y + b1, y1, t1, l1, g1);
-      loss_term<LOSS>(z.z + b2, y2, t2, l2, g2);
+      loss_term<LOSS>(z.x + b0, y0, t0, l0, g0, gv0);
+      loss_term<LOSS>(z.y + b1, y1, t1, l1, g1, gv1);
+      loss_term<LOSS>(z.z + b2, y2, t2, l2, g2, gv2);
       lsum += l0 + l1 + l2;
       const int at = (t1 > t0) ? ((t2 > t1) ? 2 : 1) : ((t2 > t0) ? 2 : 0);
       const int ap = (y1 > y0) ? ((y2 > y1) ? 2 : 1) : ((y2 > y0) ? 2 : 0);
@@ -1244,7 +1262,7 @@ extern "C" int cnnitmo_head_fwd(int dtype, const void* x, int n, int h, int h_va
 template <int LOSS>
 static int head_fwd_bwd_t(int dtype, const void* x, int n, int h, int h_valid, int w, int cin, const float* wt,
                           const float* b, const float* scale, const float* shift, const float* target, void* dx,
-                          float* g3, float* part, double grad_numel, void* stream) {
+                          float* g3, float* part, double grad_numel, void* stream, const float* given = nullptr) {
   hipStream_t s = (hipStream_t)stream;
   const int VE = dtype == CNNITMO_BF16 ? 8 : 4;
   CNN_REQUIRE(cin % VE == 0 && (cin / VE) <= 64 && ((cin / VE) & (cin / VE - 1)) == 0,
@@ -1253,16 +1271,17 @@ static int head_fwd_bwd_t(int dtype, const void* x, int n, int h, int h_valid, i
   CNN_REQUIRE(P < (1L << 31), "head: too many pixels");
   const int G = cnnitmo_head_rows(P);
   const double numel = grad_numel > 0.0 ? grad_numel : (double)n * h_valid * w * 3;
-  const float inv_numel = (float)(1.0 / numel);
-  if (launch_head2<true, LOSS>(dtype, x, n, h, h_valid, w, cin, wt, b, target, nullptr, dx, inv_numel, part, scale,
+  const float inv_numel = LOSS == CNNITMO_LOSS_GIVEN ? 1.f : (float)(1.0 / numel);
+  float* gy = const_cast<float*>(given);  // CNNITMO_LOSS_GIVEN: read through the kernels' yhat argument
+  if (launch_head2<true, LOSS>(dtype, x, n, h, h_valid, w, cin, wt, b, target, gy, dx, inv_numel, part, scale,
                                shift, g3, G, s))
     return cnnitmo_check_launch("head_fwd_bwd");
   if (dtype == CNNITMO_BF16)
     hipLaunchKernelGGL((head_kernel<bf16, true, LOSS>), dim3(G), dim3(256), 0, s, (const bf16*)x, n, h,
-                       h_valid, w, cin, wt, b, target, nullptr, (bf16*)dx, inv_numel, part, scale, shift, g3);
+                       h_valid, w, cin, wt, b, target, gy, (bf16*)dx, inv_numel, part, scale, shift, g3);
   else
     hipLaunchKernelGGL((head_kernel<float, true, LOSS>), dim3(G), dim3(256), 0, s, (const float*)x, n, h,
-                       h_valid, w, cin, wt, b, target, nullptr, (float*)dx, inv_numel, part, scale, shift, g3);
+                       h_valid, w, cin, wt, b, target, gy, (float*)dx, inv_numel, part, scale, shift, g3);
   return cnnitmo_check_launch("head_fwd_bwd");
 }
 
@@ -1286,6 +1305,16 @@ extern "C" int cnnitmo_head_fwd_bwd_loss(int loss, int dtype, const void* x, int
 #undef HEAD_LOSS
   return head_fwd_bwd_t<CNNITMO_LOSS_MSE>(dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, dx, g3, part,
                                           grad_numel, stream);
+}
+
+extern "C" int cnnitmo_head_fwd_bwd_given(int dtype, const void* x, int n, int h, int h_valid, int w, int cin,
+                                          const float* wt, const float* b, const float* scale, const float* shift,
+                                          const float* target, const float* dy, void* dx, float* g3, float* part,
+                                          void* stream) {
+  CNN_REQUIRE(dy, "head_fwd_bwd_given: null dy");
+  CNN_REQUIRE((dx != nullptr) != (g3 != nullptr), "head_fwd_bwd_given: exactly one of dx and g3 must be given");
+  return head_fwd_bwd_t<CNNITMO_LOSS_GIVEN>(dtype, x, n, h, h_valid, w, cin, wt, b, scale, shift, target, dx, g3, part,
+                                            0.0, stream, dy);
 }
 
 extern "C" int cnnitmo_head_fwd_bwd(int dtype, const void* x, int n, int h, int h_valid, int w,

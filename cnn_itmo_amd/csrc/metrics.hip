@@ -11,7 +11,8 @@
 // 3 floats apart, so the kernel works on "float columns": the SSIM map of an image is
 // (h-10) rows x 3*(w-10) columns, column j reading input columns j + 3k, k = 0..10.
 //
-// ssim_mse_kernel: one workgroup owns TR x TC positions of that map.  It stages the
+// ssim_mse_kernel (its body is ssim_tile.h's tile_pass, which the DSSIM loss of dssim.hip
+// shares): one workgroup owns TR x TC positions of that map.  It stages the
 // (TR+10) x (TC+30) input window of both images through LDS (16-byte loads where the row
 // pitch allows them), accumulating (a-b)^2 of the elements it owns on the way (its own
 // TR x TC corner; the last tile row / column also own the 10-row / 30-column apron, so
@@ -40,185 +41,19 @@
 
 #pragma clang fp contract(off)
 
+#include "ssim_tile.h"
+
 namespace {
 
-constexpr int NT = 256;                  // threads per workgroup
-constexpr int TR = 16;                   // map rows per tile
-constexpr int TC = 48;                   // map float-columns per tile (16 pixels)
-constexpr int R = 5;                     // window radius: 11 taps
-constexpr int NTAP = 2 * R + 1;
-constexpr int IR = TR + 2 * R;           // staged input rows: 26
-constexpr int IC = TC + 3 * 2 * R;       // staged input float-columns: 78
-constexpr int ICP = 80;                  // padded to whole 16-byte chunks
-constexpr int G = 4;                     // outputs per thread in either pass
-constexpr int GW = G + 2 * R;            // inputs those outputs share: 14
+using namespace ssim_tile;                // the tile, its staging and the separable fp64 filter (ssim_tile.h)
 constexpr int MSE_BLK = 128;             // workgroups per image of mse_kernel
-static_assert(TC % (3 * G) == 0 && TR % G == 0 && ICP % 4 == 0 && ICP >= IC && TC % 4 == 0, "tile");
-
-struct Taps {
-  double g[NTAP];
-};
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum of (v0, v1) over the workgroup -> thread 0
-__device__ __forceinline__ void block_sum2(double& v0, double& v1, double (*sh)[2]) {
-  v0 = wave_sum_f64(v0);
-  v1 = wave_sum_f64(v1);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-    sh[wave][0] = v0;
-    sh[wave][1] = v1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    v0 = sh[0][0];
-    v1 = sh[0][1];
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
-      v0 += sh[i][0];
-      v1 += sh[i][1];
-    }
-  }
-}
 
 // part [n][nblk][2] = (ssim sum, squared-error sum) of a tile; grid (tiles_x, tiles_y, n)
 template <bool VEC>
 __global__ __launch_bounds__(NT) void ssim_mse_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                       int h, int w, Taps tp, double c1, double c2,
                                                       double* __restrict__ part) {
-  __shared__ float sa[IR][ICP];
-  __shared__ float sb[IR][ICP];
-  __shared__ double hs[5][IR][TC];
-  __shared__ double red[NT / 64][2];
-
-  const int tid = threadIdx.x;
-  const int w3 = 3 * w;
-  const int mh = h - 2 * R, mw3 = 3 * (w - 2 * R);  // the map's size
-  const int r0 = blockIdx.y * TR, c0 = blockIdx.x * TC;
-  const long img = (long)blockIdx.z * h * w3;
-  // rows / columns of the staged window whose squared error this tile counts
-  const int own_r = blockIdx.y == gridDim.y - 1 ? IR : TR;
-  const int own_c = blockIdx.x == gridDim.x - 1 ? ICP : TC;
-
-  double sq = 0.0;
-  if (VEC) {  // w3 % 4 == 0 and 16-byte aligned bases: a chunk is inside the row or outside it
-    for (int i = tid; i < IR * (ICP / 4); i += NT) {
-      const int r = i / (ICP / 4), c = (i % (ICP / 4)) * 4;
-      const int gr = r0 + r, gc = c0 + c;
-      float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
-      if (gr < h && gc < w3) {
-        const long o = img + (long)gr * w3 + gc;
-        va = *reinterpret_cast<const float4*>(a + o);
-        vb = *reinterpret_cast<const float4*>(b + o);
-        if (r < own_r && c < own_c) {
-          const double d0 = (double)va.x - (double)vb.x, d1 = (double)va.y - (double)vb.y;
-          const double d2 = (double)va.z - (double)vb.z, d3 = (double)va.w - (double)vb.w;
-          sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        }
-      }
-      *reinterpret_cast<float4*>(&sa[r][c]) = va;
-      *reinterpret_cast<float4*>(&sb[r][c]) = vb;
-    }
-  } else {
-    for (int i = tid; i < IR * ICP; i += NT) {
-      const int r = i / ICP, c = i % ICP;
-      const int gr = r0 + r, gc = c0 + c;
-      float va = 0.f, vb = 0.f;
-      if (gr < h && gc < w3) {
-        const long o = img + (long)gr * w3 + gc;
-        va = a[o];
-        vb = b[o];
-        if (r < own_r && c < own_c) {
-          const double d = (double)va - (double)vb;
-          sq += d * d;
-        }
-      }
-      sa[r][c] = va;
-      sb[r][c] = vb;
-    }
-  }
-  __syncthreads();
-
-  // horizontal pass: thread = (row, base column cb); outputs cb + 3t, t < G, from inputs cb + 3m, m < GW
-  for (int i = tid; i < IR * (TC / G); i += NT) {
-    const int r = i / (TC / G), gi = i % (TC / G);
-    const int cb = (gi / 3) * (3 * G) + gi % 3;
-    double acc[5][G];
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-#pragma unroll
-      for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
-#pragma unroll
-    for (int m = 0; m < GW; ++m) {
-      const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
-      const double xx = x * x, yy = y * y, xy = x * y;
-#pragma unroll
-      for (int t = 0; t < G; ++t) {
-        if (m - t >= 0 && m - t < NTAP) {
-          const double g = tp.g[m - t];
-          acc[0][t] = fma(g, x, acc[0][t]);
-          acc[1][t] = fma(g, y, acc[1][t]);
-          acc[2][t] = fma(g, xx, acc[2][t]);
-          acc[3][t] = fma(g, yy, acc[3][t]);
-          acc[4][t] = fma(g, xy, acc[4][t]);
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-#pragma unroll
-      for (int t = 0; t < G; ++t) hs[k][r][cb + 3 * t] = acc[k][t];
-  }
-  __syncthreads();
-
-  // vertical pass: thread = (row group, column); outputs rows 4*rg + t from row sums 4*rg + m
-  double ss = 0.0;
-  for (int i = tid; i < (TR / G) * TC; i += NT) {
-    const int rb = (i / TC) * G, c = i % TC;
-    if (r0 + rb >= mh || c0 + c >= mw3) continue;
-    double acc[5][G];
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-#pragma unroll
-      for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
-#pragma unroll
-    for (int m = 0; m < GW; ++m) {
-      double v[5];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) v[k] = hs[k][rb + m][c];
-#pragma unroll
-      for (int t = 0; t < G; ++t) {
-        if (m - t >= 0 && m - t < NTAP) {
-          const double g = tp.g[m - t];
-#pragma unroll
-          for (int k = 0; k < 5; ++k) acc[k][t] = fma(g, v[k], acc[k][t]);
-        }
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < G; ++t) {
-      if (r0 + rb + t < mh) {
-        const double mx = acc[0][t], my = acc[1][t];
-        const double mxx = mx * mx, myy = my * my, mxy = mx * my;
-        const double vx = acc[2][t] - mxx, vy = acc[3][t] - myy, cxy = acc[4][t] - mxy;
-        const double num = (2.0 * mxy + c1) * (2.0 * cxy + c2);
-        const double den = (mxx + myy + c1) * (vx + vy + c2);
-        ss += num / den;
-      }
-    }
-  }
-
-  block_sum2(ss, sq, red);
-  if (tid == 0) {
-    const long nblk = (long)gridDim.x * gridDim.y;
-    double* d = part + ((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-    d[0] = ss;
-    d[1] = sq;
-  }
+  tile_pass<VEC, SQUARED_ERROR>(a, b, h, w, 0, tp, c1, c2, part, nullptr);
 }
 
 // part [n][MSE_BLK][2] = (0, squared-error sum); len = h*w*3 elements per image; grid (MSE_BLK, n)
@@ -281,19 +116,13 @@ __global__ __launch_bounds__(NT) void metrics_final_kernel(const double* __restr
   }
 }
 
-long tiles_of(int h, int w) {
-  if (h < NTAP || w < NTAP) return 0;
-  const long ty = (h - 2 * R + TR - 1) / TR, tx = (3L * (w - 2 * R) + TC - 1) / TC;
-  return ty * tx;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+long tiles_or_none(int h, int w) { return h < NTAP || w < NTAP ? 0 : tiles_of(h, w); }
 
 }  // namespace
 
 extern "C" long cnnitmo_image_metrics_workspace_bytes(int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return 0;
-  return (long)n * std::max<long>(tiles_of(h, w), MSE_BLK) * 2 * (long)sizeof(double);
+  return (long)n * std::max<long>(tiles_or_none(h, w), MSE_BLK) * 2 * (long)sizeof(double);
 }
 
 extern "C" int cnnitmo_image_metrics(int what, const float* a, const float* b, int n, int h, int w, double max_val,
@@ -314,10 +143,7 @@ extern "C" int cnnitmo_image_metrics(int what, const float* a, const float* b, i
   long nblk;
   double n_pos = 1.0;
   if (what & 2) {
-    Taps tp;
-    double sum = 0.0;
-    for (int i = 0; i < NTAP; ++i) sum += tp.g[i] = exp(-(double)((i - R) * (i - R)) / 4.5);
-    for (int i = 0; i < NTAP; ++i) tp.g[i] /= sum;
+    const Taps tp = make_taps();
     const double c1 = (0.01 * max_val) * (0.01 * max_val), c2 = (0.03 * max_val) * (0.03 * max_val);
     const dim3 grid((unsigned)((3L * (w - 2 * R) + TC - 1) / TC), (unsigned)((h - 2 * R + TR - 1) / TR), n);
     nblk = (long)grid.x * grid.y;

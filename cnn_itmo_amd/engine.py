@@ -37,6 +37,7 @@ import torch
 from . import ops
 from . import optimizers as O
 from . import _lib as L
+from .losses import DSSIM
 from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2DTranspose, Dropout,
                      InputLayer, MaxPooling2D)
 
@@ -699,9 +700,30 @@ class HeadStage(Stage):
         return (e.training and v.folded and v.sum_consumers == 1 and not v.place and prod is not None
                 and prod.bn is not None and prod.drop is None and prod.kind == "c3")
 
-    def loss_and_grad(self, n, target, loss_acc, grad_numel=0.0):
+    def _dssim_check(self, target):
+        e = self.eng
+        shape = (target.shape[0], e.h_valid, self.vin.w, 3)
+        if tuple(target.shape) != shape:
+            raise ValueError(f"DSSIM loss: target of shape {tuple(target.shape)}, prediction {shape}")
+        if e.h_valid < 11 or self.vin.w < 11:
+            raise ValueError(f"DSSIM loss: a frame of {e.h_valid} x {self.vin.w} valid pixels is smaller than "
+                             f"SSIM's 11 x 11 window")
+
+    def dssim_loss(self, n, target, loss_acc, yhat):
+        """The DSSIM loss and 'accuracy' of a prediction already in yhat, without a backward
+        kernel (evaluate_batch): loss_acc = [mean L_i, accuracy]."""
+        e = self.eng
+        self._dssim_check(target)
+        d = e.dssim
+        out = ops.dssim_loss_grad(d.base_id, d.alpha, yhat, target)
+        count = ops.rgb_accuracy(yhat, target, torch.zeros(1, device=e.device, dtype=torch.int64))
+        loss_acc[0] = out[:, 2].mean()
+        loss_acc[1] = count[0] / float(yhat.numel() // 3)
+
+    def loss_and_grad(self, n, target, loss_acc, grad_numel=0.0, grad_frames=0.0):
         """The model's loss (Engine.loss_id), 'accuracy' and the head's gradients.
-        grad_numel: the loss gradient's normaliser (0: this batch's element count)."""
+        grad_numel: the loss gradient's normaliser (0: this batch's element count);
+        grad_frames: the same in frames, for the DSSIM losses."""
         e = self.eng
         P = n * self.vin.h * self.vin.w
         rows = ops.head_rows(P)
@@ -709,7 +731,25 @@ class HeadStage(Stage):
         aff = self.vin.coef() if e.training and self.vin.folded else None
         wt = e.p(self.name + "/kernel")
         loss = e.loss_id  # 'mse' keeps its own entry points (the same kernels)
-        if self._rank3():
+        dssim_out = None
+        if loss == L.LOSS_GIVEN:
+            # DSSIM: the prediction, its loss and dL/dy, then the head with that gradient given
+            self._dssim_check(target)
+            d = e.dssim
+            y = torch.empty(n, e.h_valid, self.vin.w, 3, device=e.device, dtype=torch.float32)
+            ops.head_fwd(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), y, aff)
+            dy = torch.empty_like(y)
+            dssim_out = ops.dssim_loss_grad(d.base_id, d.alpha, y, target, dy, grad_frames)
+            if self._rank3():
+                g3 = torch.empty(P * 3, device=e.device, dtype=torch.float32)
+                ops.head_fwd_bwd_given(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, dy,
+                                       part, g3=g3, aff=aff)
+                self.vin.grad_g3 = (g3, wt)
+            else:
+                self.vin.ensure_grad(n, e.tdtype, e.device)
+                ops.head_fwd_bwd_given(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, dy,
+                                       part, dx=self.vin.gview(n).buf, aff=aff)
+        elif self._rank3():
             g3 = torch.empty(P * 3, device=e.device, dtype=torch.float32)
             if loss == L.LOSSES["mse"]:
                 ops.head_fwd_bwd_g3(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, g3,
@@ -732,6 +772,8 @@ class HeadStage(Stage):
             if e.training and v.sum_consumers and v.folded else None
         ops.head_finalize(part, rows, self.cin, n * e.h_valid * self.vin.w * 3, loss_acc,
                           e.g(self.name + "/kernel"), e.g(self.name + "/bias"), aff, raw=raw)
+        if dssim_out is not None:  # (the head's own loss slot is 0)
+            loss_acc[0] = dssim_out[:, 2].mean()
         if raw is not None:
             pm = torch.empty(L.CONSUMER_ROWS * 2 * v.c, device=e.device, dtype=torch.float32)
             ops.bn_consumer_sums(3, e.p(self.name + "/kernel"), raw, 3, self.cin, 0, v.c, e.g(self.name + "/bias"),
@@ -1012,8 +1054,17 @@ class Engine:
     # ---- loss / optimizer state ---------------------------------------------
     @property
     def loss_id(self):
-        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile)."""
+        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile); a DSSIM loss is
+        CNNITMO_LOSS_GIVEN: the head takes its gradient from cnnitmo_dssim_loss_grad."""
+        if self.dssim is not None:
+            return L.LOSS_GIVEN
         return L.LOSSES[getattr(self.model, "loss", None) or "mse"]
+
+    @property
+    def dssim(self):
+        """The model's losses.DSSIM, or None with a pointwise loss."""
+        loss = getattr(self.model, "loss", None)
+        return loss if isinstance(loss, DSSIM) else None
 
     def ensure_slots(self, k):
         """At least k optimizer slot buffers (new ones zero, as Keras creates them)."""
@@ -1132,7 +1183,8 @@ class Engine:
         loss_acc = torch.empty(2, device=self.device, dtype=torch.float32)
         head = self.stages[-1]
         gn = 0.0 if grad_frames is None else float(grad_frames) * self.h_valid * self.model.inputs[0].shape[1] * 3
-        head.loss_and_grad(n, target.contiguous().float(), loss_acc, gn)
+        head.loss_and_grad(n, target.contiguous().float(), loss_acc, gn,
+                           0.0 if grad_frames is None else float(grad_frames))
         if self.grad_hook:  # (DP all-reduce launches behind the stage's gradient writes)
             self.grad_hook(*self.stage_goff[-1])
         for i in range(len(self.stages) - 2, -1, -1):
@@ -1157,32 +1209,51 @@ class Engine:
         tensor of the prediction against the target's valid rows (cnnitmo_image_metrics).  The
         loss path is the same calls either way; the prediction is then written the way predict()
         writes it (the head in its producer's epilogue where fused, the head kernel otherwise)
-        from the activations this forward left."""
-        n = self.forward(x, training=False)
-        loss_acc = torch.empty(2, device=self.device, dtype=torch.float32)
-        saved = self.grads.clone()
-        target = target.contiguous().float()
-        self.stages[-1].loss_and_grad(n, target, loss_acc)
-        self.grads.copy_(saved)
-        if not image_metrics:
-            self._release()
-            return loss_acc
+        from the activations this forward left.  A DSSIM loss is a function of the prediction:
+        it is written first, then cnnitmo_dssim_loss_grad's loss-only form and
+        cnnitmo_rgb_accuracy give [loss, acc]; no backward kernel runs."""
         cols = {"psnr": 1, "ssim": 2}
         if any(k not in cols for k in image_metrics):
             raise ValueError(f"image_metrics {image_metrics!r}: names out of {sorted(cols)}")
         head = self.stages[-1]
-        yhat = torch.empty(n, self.h_valid, self.model.inputs[0].shape[1], 3, device=self.device,
-                           dtype=torch.float32)
-        if tuple(target.shape) != tuple(yhat.shape):
-            raise ValueError(f"image metrics: target of shape {tuple(target.shape)}, prediction {tuple(yhat.shape)}")
-        if head.fused:
+        target = target.contiguous().float()
+        loss_acc = torch.empty(2, device=self.device, dtype=torch.float32)
+        if self.dssim is not None:
+            # a DSSIM loss is a function of the prediction: write it as predict() does (a fused
+            # head in its producer's epilogue during the forward) and take the loss-only call
+            yhat = torch.empty(x.shape[0], x.shape[1], self.model.inputs[0].shape[1], 3, device=self.device,
+                               dtype=torch.float32)
             self._yhat = yhat
             try:
-                head.vin.producer.forward(n, False)
+                n = self.forward(x, training=False)
             finally:
                 self._yhat = None
-        head.infer(n, yhat)
-        self._release()
+            head.infer(n, yhat)
+            self._release()
+            head.dssim_loss(n, target, loss_acc, yhat)
+            if not image_metrics:
+                return loss_acc
+        else:
+            n = self.forward(x, training=False)
+            saved = self.grads.clone()
+            head.loss_and_grad(n, target, loss_acc)
+            self.grads.copy_(saved)
+            if not image_metrics:
+                self._release()
+                return loss_acc
+            yhat = torch.empty(n, self.h_valid, self.model.inputs[0].shape[1], 3, device=self.device,
+                               dtype=torch.float32)
+            if tuple(target.shape) != tuple(yhat.shape):
+                raise ValueError(f"image metrics: target of shape {tuple(target.shape)}, prediction "
+                                 f"{tuple(yhat.shape)}")
+            if head.fused:
+                self._yhat = yhat
+                try:
+                    head.vin.producer.forward(n, False)
+                finally:
+                    self._yhat = None
+            head.infer(n, yhat)
+            self._release()
         what = (ops.MSE_PSNR if "psnr" in image_metrics else 0) | (ops.SSIM if "ssim" in image_metrics else 0)
         out = ops.image_metrics(what, yhat, target, 1.0)
         return loss_acc, out[:, [cols[k] for k in image_metrics]]

@@ -31,7 +31,7 @@ import json
 
 import numpy as np
 
-from . import hdf5
+from . import hdf5, losses
 from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2DTranspose, Dropout,
                      InputLayer, MaxPooling2D)
 
@@ -126,7 +126,7 @@ def training_config(model):
     # the compiled metrics in order ('accuracy', 'psnr', 'ssim'); load_model compiles with them
     metrics = [_METRIC_CONFIG[k] for k in getattr(model, "metrics_names", [])[1:]]
     return {"optimizer_config": {"class_name": o.class_name, "config": o.get_config()},
-            "loss": model.loss, "metrics": metrics,
+            "loss": losses.serialize(model.loss), "metrics": metrics,
             "sample_weight_mode": None, "loss_weights": None}
 
 

@@ -29,7 +29,8 @@ from .layers import (LAYER_CLASSES, BatchNormalization, Conv2D, Conv2DTranspose,
                      Layer)
 
 
-from . import optimizers
+from . import losses, optimizers
+from .losses import DSSIM  # noqa: F401
 from .optimizers import SGD, Adam, RMSprop  # noqa: F401  (keras.optimizers names, re-exported)
 
 # compile()'s loss names -> the canonical name (Model.loss, _lib.LOSSES)
@@ -98,7 +99,7 @@ class Model:
         self.layers = sorted(seen.values(), key=lambda l: l.seq)
         self._weights = {}  # internal-layout numpy weights (host copy, authoritative before engine)
         self.optimizer = None
-        self.loss = None         # canonical loss name once compiled
+        self.loss = None         # once compiled: the canonical loss name, or a losses.DSSIM
         self.engine = None
         self._dp = None          # dist.GradBucketer once distribute() was called
         self._dp_args = None
@@ -162,10 +163,12 @@ class Model:
     def compile(self, optimizer="rmsprop", loss="mse", metrics=None, dtype=None, **kwargs):
         """optimizer: 'rmsprop' / 'adam' / 'sgd' (any case) or an RMSprop / Adam / SGD instance;
         loss: 'mse', 'mae', 'logcosh', 'msle', 'binary_crossentropy' or a Keras alias of one
-        (_LOSS_NAMES).  Nothing changes when an argument is refused."""
+        (_LOSS_NAMES); 'dssim' (1 - SSIM) or a losses.DSSIM(base, alpha), which ``Model.loss``
+        then holds.  Nothing changes when an argument is refused."""
         optimizer = optimizers.get(optimizer)
-        if not isinstance(loss, str) or loss not in _LOSS_NAMES:
-            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES)})")
+        dssim = losses.get(loss)
+        if dssim is None and (not isinstance(loss, str) or loss not in _LOSS_NAMES):
+            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES) + ['dssim']} or a DSSIM)")
         if dtype not in (None, "float32", "bfloat16"):
             raise ValueError("dtype must be 'float32' or 'bfloat16'")
         names = []
@@ -179,7 +182,7 @@ class Model:
                 s.zero_()
             self.engine.iterations = 0
         self.optimizer = optimizer
-        self.loss = _LOSS_NAMES[loss]
+        self.loss = dssim if dssim is not None else _LOSS_NAMES[loss]
         self.metrics_names = ["loss"] + names
         # 'psnr' / 'ssim' in the order given: computed by evaluate() and for the validation logs
         self.image_metrics = [k for k in names if k != "acc"]
@@ -561,7 +564,7 @@ class Model:
             arrays["opt/dtype"] = np.frombuffer(self.dtype.encode(), np.uint8)
         if self.optimizer is not None:
             o = self.optimizer
-            cfg = {"class_name": o.class_name, "config": o.get_config(), "loss": self.loss,
+            cfg = {"class_name": o.class_name, "config": o.get_config(), "loss": losses.serialize(self.loss),
                    "metrics": [_METRIC_CONFIG[k] for k in self.metrics_names[1:]]}
             arrays["opt/config"] = np.frombuffer(json.dumps(cfg).encode(), np.uint8)
         tmp = path + ".tmp.npz"

@@ -366,6 +366,14 @@ def head_fwd_bwd_loss(loss, dt, x: View, h_valid, wt, b, target, part, dx=None, 
          ptr(sh), ptr(target), ptr(dx), ptr(g3), ptr(part), float(grad_numel), stream_ptr())
 
 
+def head_fwd_bwd_given(dt, x: View, h_valid, wt, b, target, dy, part, dx=None, g3=None, aff=None):
+    """head_fwd_bwd (dx) or head_fwd_bwd_g3 (g3) with the loss gradient dy [n, h_valid, w, 3] given,
+    already normalised; the loss slot of part is 0 (cnnitmo_head_fwd_bwd_given)."""
+    sc, sh = aff if aff is not None else (None, None)
+    call("cnnitmo_head_fwd_bwd_given", dt, x.ptr, x.n, x.h, h_valid, x.w, x.c, ptr(wt), ptr(b), ptr(sc),
+         ptr(sh), ptr(target), ptr(dy), ptr(dx), ptr(g3), ptr(part), stream_ptr())
+
+
 def bn_bwd_apply_g3(dt, g3, wh, r, c, p, coef, dz, part):
     rp, rld, roff = _rview(r, c)
     call("cnnitmo_bn_bwd_apply_g3", dt, ptr(g3), ptr(wh), rp, rld, roff, p, c, ptr(coef), ptr(dz), ptr(part),
@@ -451,6 +459,35 @@ def image_metrics(what, a, b, max_val=1.0, out=None):
     call("cnnitmo_image_metrics", what, ptr(a), ptr(b), n, h, w, float(max_val), ptr(out), ws.data_ptr(),
          ws.numel(), stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------- DSSIM loss
+def dssim_workspace_bytes(n, h, w, with_grad):
+    return query("cnnitmo_dssim_workspace_bytes", n, h, w, int(bool(with_grad)))
+
+
+def dssim_loss_grad(base, alpha, y, t, dy=None, grad_frames=0.0, out=None):
+    """y, t [n,h,w,3] contiguous fp32 device tensors -> out [n,3] fp64 = (ssim, base term, loss) per
+    image; dy (optional, like y) = the gradient of the batch-mean loss, normalised by grad_frames
+    (0: n) frames (cnnitmo_dssim_loss_grad).  base: an L.DSSIM_BASES id."""
+    n, h, w, c = y.shape
+    assert c == 3 and tuple(t.shape) == (n, h, w, 3), (tuple(y.shape), tuple(t.shape))
+    assert y.dtype == torch.float32 and t.dtype == torch.float32 and y.is_contiguous() and t.is_contiguous()
+    assert dy is None or (dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (n, h, w, 3))
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float64, device=y.device)
+    ws = workspace(dssim_workspace_bytes(n, h, w, dy is not None), y.device)
+    call("cnnitmo_dssim_loss_grad", base, float(alpha), ptr(y), ptr(t), n, h, w, float(grad_frames), ptr(out),
+         ptr(dy), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out
+
+
+def rgb_accuracy(y, t, count):
+    """count (int64 [1], device) += the pixels of y, t [..., 3] whose argmax over RGB agrees."""
+    assert y.dtype == torch.float32 and t.dtype == torch.float32 and y.is_contiguous() and t.is_contiguous()
+    assert y.shape == t.shape and y.shape[-1] == 3 and count.dtype == torch.int64
+    call("cnnitmo_rgb_accuracy", ptr(y), ptr(t), y.numel() // 3, ptr(count), stream_ptr())
+    return count
 
 
 # ---------------------------------------------------------------- RGBE codec

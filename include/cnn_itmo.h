@@ -457,6 +457,16 @@ int cnnitmo_head_fwd_bwd_loss(int loss, int dtype, const void* x, int n, int h, 
                               const float* wt, const float* b, const float* scale, const float* shift,
                               const float* target, void* dx /*nullable*/, float* g3 /*nullable*/,
                               float* part, double grad_numel, void* stream);
+/* The same call with the loss gradient given from outside: dy [n][h_valid][w][3] fp32 =
+ * dL/dyhat, already normalised (no grad_numel), e.g. cnnitmo_dssim_loss_grad's.
+ * dl/dz = dy * y(1-y); the loss slot of part (and of cnnitmo_head_finalize) is 0, 'accuracy'
+ * comes from target as for every other loss; dx / g3, dW, db and the part layout are the
+ * same.  CNNITMO_LOSS_GIVEN is refused by cnnitmo_head_fwd_bwd_loss, which has no dy. */
+#define CNNITMO_LOSS_GIVEN 5
+int cnnitmo_head_fwd_bwd_given(int dtype, const void* x, int n, int h, int h_valid, int w, int cin,
+                               const float* wt, const float* b, const float* scale, const float* shift,
+                               const float* target, const float* dy, void* dx /*nullable*/,
+                               float* g3 /*nullable*/, float* part, void* stream);
 
 /* ---------------------------------------------------------------------------
  * RMSprop (keras.optimizers.RMSprop defaults via compile('rmsprop'), model.py:281):
@@ -534,6 +544,36 @@ int cnnitmo_inverse_reinhard_apply(int mode, const void* sdr, int n, int h, int 
 long cnnitmo_image_metrics_workspace_bytes(int n, int h, int w);
 int cnnitmo_image_metrics(int what, const float* a, const float* b, int n, int h, int w, double max_val,
                           double* out, void* workspace, long workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Structural-dissimilarity training loss of a prediction y against a target t
+ * (fp32 [n][h][w][3], contiguous, max_val 1), per image i:
+ *   L_i = alpha (1 - SSIM_i) + (1 - alpha) B_i
+ *   B_i = mean over h*w*3 of |y-t| (CNNITMO_BASE_MAE), of (y-t)^2 (CNNITMO_BASE_MSE),
+ *         0 with CNNITMO_BASE_NONE (alpha must then be 1); alpha in [0, 1].
+ * SSIM_i is cnnitmo_image_metrics' (same window, constants and valid positions).
+ * out (device): double [n][3] = {ssim, B, L}.  dy (nullable, fp32 [n][h][w][3]) =
+ * d(sum_i L_i / F)/dy, F = grad_frames (<= 0: n), the frame count the gradient is
+ * normalised by (the role grad_numel plays for the pointwise losses); every element
+ * is written exactly once, sign(0) = 0 for the MAE base.  A null dy gives the loss
+ * only: the same out bit for bit, no coefficient planes written.
+ * fp64 after the loads, fixed-order reductions, no atomics: bitwise reproducible.
+ * Requires h >= 11 and w >= 11.  workspace: cnnitmo_dssim_workspace_bytes(n, h, w,
+ * with_grad) bytes of device memory, 8-byte aligned, its contents irrelevant
+ * (<= 0 for a bad shape; the query needs no GPU); with_grad 0: loss only.
+ * Stateless, never allocates; bad arguments are CNNITMO_EINVAL before any launch.
+ */
+#define CNNITMO_BASE_NONE 0
+#define CNNITMO_BASE_MAE 1
+#define CNNITMO_BASE_MSE 2
+long cnnitmo_dssim_workspace_bytes(int n, int h, int w, int with_grad);
+int cnnitmo_dssim_loss_grad(int base, double alpha, const float* y, const float* t, int n, int h, int w,
+                            double grad_frames, double* out, float* dy, void* workspace, long workspace_bytes,
+                            void* stream);
+/* 'accuracy' of the head without a backward kernel: *count (device, zeroed by the caller) +=
+ * the pixels out of npix whose argmax over RGB agrees between y and t [npix][3] fp32, with
+ * the head kernels' tie rule (the first of equal channels). */
+int cnnitmo_rgb_accuracy(const float* y, const float* t, long npix, unsigned long long* count, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Radiance RGBE (.hdr / .pic) pixel codec: [npix][3] fp32 <-> [npix][4] bytes
