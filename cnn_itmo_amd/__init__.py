@@ -12,8 +12,9 @@ from .losses import DSSIM
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import CSVLogger, LambdaCallback, ModelCheckpoint
 from . import hdrio, metrics
+from .hdrgen import HDRPairGenerator, HDRPairIterator
 
-__all__ = ["Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
+__all__ = ["HDRPairGenerator", "HDRPairIterator","Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
            "Adam", "SGD", "DSSIM", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
            "LambdaCallback", "ModelCheckpoint", "metrics", "hdrio"]

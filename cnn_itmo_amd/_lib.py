@@ -132,6 +132,8 @@ SIGNATURES = {
     "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),
     "cnnitmo_rgbe_encode": (i32, [vp, i64, vp, vp]),
     "cnnitmo_rgbe_decode": (i32, [vp, i64, vp, vp]),
+    "cnnitmo_hdr_pairs_workspace_bytes": (sz, [i32]),
+    "cnnitmo_hdr_pairs": (i32, [vp, i32, i32, i32, vp, vp, vp, f64, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
 }
 
 

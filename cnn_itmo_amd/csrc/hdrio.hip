@@ -29,6 +29,7 @@
 // is not 16-byte aligned (nvec = 0), take the one-pixel path of the same kernel; all paths call
 // the same per-component functions, so they give the same bytes.
 #include "common.h"
+#include "rgbe_px.h"
 
 namespace {
 
@@ -60,19 +61,7 @@ __device__ __forceinline__ uint32_t encode_px(float r, float g, float b) {
   return mant_of(ur, bv) | (mant_of(ug, bv) << 8) | (mant_of(ub, bv) << 16) | ((bv + 2u) << 24);
 }
 
-__device__ __forceinline__ float decode_c(uint32_t m, uint32_t E) {
-  if (m == 0u) return 0.f;
-  const int p = 31 - __builtin_clz(m);  // 0..7
-  const int be = p + (int)E - 9;        // biased fp32 exponent of m * 2^(E - 136); <= 253
-  if (be >= 1) return __uint_as_float(((uint32_t)be << 23) | ((m << (23 - p)) & 0x7FFFFFu));
-  return __uint_as_float(m << (E + 13u));  // denormal: m * 2^(E - 136) = (m << (E + 13)) * 2^-149
-}
-
-// channel ch (0..2) of the pixel code q
-__device__ __forceinline__ float decode_ch(uint32_t q, int ch) {
-  const uint32_t E = q >> 24;
-  return E == 0u ? 0.f : decode_c((q >> (8 * ch)) & 255u, E);
-}
+// decode_c / decode_ch: rgbe_px.h
 
 __device__ __forceinline__ void decode_px(uint32_t q, float& r, float& g, float& b) {
   r = decode_ch(q, 0);

@@ -24,6 +24,7 @@
 // HBM-bound: 12 B read + 12 B (fp32) / 3 B (u8) written per pixel per map; the
 // statistics pass reads 12 B (fp32) or 3 B (u8) per pixel.
 #include "common.h"
+#include "tonemap_px.h"  // Lum, lum, REALMIN, im2uint8, lum_of
 
 // no FMA contraction: the products and sums round like MATLAB's (and numpy's) doubles
 #pragma clang fp contract(off)
@@ -32,13 +33,6 @@ namespace {
 
 constexpr int TB = 256;  // threads per block
 constexpr int BLK_PER_IMG = 256;  // blocks per image in the statistics pass
-constexpr double REALMIN = 2.2250738585072014e-308;
-
-struct Lum {
-  double r, g, b;
-};
-
-__device__ __forceinline__ double lum(const Lum& c, double R, double G, double B) { return c.r * R + c.g * G + c.b * B; }
 
 __device__ __forceinline__ double decode_sdr(uint8_t v) { return pow((double)v / 255.0, 2.2); }
 
@@ -91,14 +85,6 @@ __global__ void stats_final_kernel(const double* __restrict__ part, int n, doubl
   }
   stats[2 * im] = s;
   stats[2 * im + 1] = z;
-}
-
-// MATLAB uint8(255*x): round half away from zero, saturate, NaN -> 0
-__device__ __forceinline__ uint8_t im2uint8(double x) {
-  const double v = 255.0 * x;
-  if (!(v > 0.0)) return 0;  // also NaN
-  if (v >= 255.0) return 255;
-  return (uint8_t)floor(v + 0.5);
 }
 
 // curve 0: Reinhard; 1: virtual camera.  params per image: [key*2^v, n, y]
@@ -173,8 +159,6 @@ __global__ __launch_bounds__(TB) void inverse_kernel(int mode, const void* __res
   o[1] = (float)(Gc * f);
   o[2] = (float)(B * f);
 }
-
-Lum lum_of(const double* c) { return c ? Lum{c[0], c[1], c[2]} : Lum{0.2126, 0.7152, 0.0722}; }
 
 }  // namespace
 

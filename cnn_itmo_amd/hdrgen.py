@@ -1,0 +1,236 @@
+"""Training pairs straight from HDR files, on the GPU: ``HDRPairGenerator``.
+
+The offline route (make_dataset, then two seed-locked ``ImageDataGenerator.flow_from_directory``
+streams) writes 8-bit PNGs of ``tonemap.reinhard`` / ``tonemap.virtual_camera`` and re-decodes and
+warps them every epoch: targets quantised to 1/255, the camera draws frozen when the data set is
+built.  Here the HDR pictures stay on the device in their file format (RGBE bytes for ``.hdr`` /
+``.pic``, fp32 for ``.pfm``) and one ``cnnitmo_hdr_pairs`` call (csrc/hdrpairs.hip) makes a batch:
+it gathers a warped window of each picture, takes its log-average and writes the virtual-camera
+input ``x`` and the Reinhard target ``y``.  No pixel is touched on the host.
+
+    gen = HDRPairGenerator(rotation_range=90, horizontal_flip=True, vertical_flip=True, zoom_range=0.2)
+    it = gen.flow_from_directory("hdr/", target_size=(512, 512), batch_size=32, seed=1)
+    model.fit_generator(it, steps_per_epoch=len(it), epochs=100)
+
+The iterator is a ``datagen.Iterator``: the same reseeding before every batch, permutation, rank
+sharding (every rank replays the draws of the whole global batch and keeps its ``_local`` share)
+and ``last_global_batch``.  Per frame of the global batch the draws are, from the iterator's
+``RandomState`` and in this order:
+
+1. ``ImageDataGenerator.get_random_transform`` at ``target_size`` (the geometric arguments);
+2. the window of ``window_size`` (default ``target_size``) inside the picture -- ``'random'``:
+   ``top = randint(0, hs-ch+1)`` then ``left = randint(0, ws-cw+1)``; ``'center'`` and ``'full'``
+   (the whole picture) draw nothing;
+3. ``cameras='random'``: ``v = 8*random_sample() - 4``, ``n = normal(0.6, sqrt(0.1))`` redrawn while
+   <= 0, then ``y = normal(0.9, sqrt(0.1))`` redrawn while <= 0.  virtual_camera.m draws n and y
+   unbounded; a non-positive one makes the curve singular, which a training stream cannot shrug off
+   as an offline tool can.  ``cameras='fixed'`` draws nothing: file j always gets element 0 of
+   ``tonemap.virtual_camera_params(1, np.random.default_rng(seed + j))``, make_dataset's
+   ``--cameras 1`` values (a seed of None counts as 0), so validation batches repeat every epoch.
+
+The matrix handed to the kernel maps an output pixel to the source picture:
+``M_src = T(top, left) . S . M_keras``, with ``M_keras`` the ``ImageDataGenerator.affine`` matrix at
+``target_size`` and ``S`` the centre-aligned resize ``src = (dst + 0.5) * (ch / H) - 0.5`` (the
+identity when the window has the target size); the bilinear taps are clamped to the window.
+
+``quantize``: ``'input'`` (default) rounds x to the 8-bit levels an SDR file has and leaves the
+target in fp32; ``'both'`` also rounds y (what the PNG route trains on); ``None`` rounds neither.
+"""
+from __future__ import annotations
+
+import concurrent.futures as cf
+import os
+import re
+
+import numpy as np
+
+from . import hdrio
+from .datagen import ImageDataGenerator, Iterator
+from .make_dataset import EXTENSIONS
+
+QUANTIZE = {None: 0, "input": 1, "both": 3}
+
+
+def image_size(path):
+    """(h, w) of a ``.hdr`` / ``.pic`` / ``.pfm`` file from its header alone."""
+    with open(path, "rb") as fh:
+        buf = fh.read(1 << 16)
+    if os.path.splitext(path)[1].lower() == ".pfm":
+        m = re.match(rb"PF\s+(\d+)\s+(\d+)\s", buf)
+        if not m:
+            raise ValueError(f"{path}: not a colour PFM file")
+        return int(m.group(2)), int(m.group(1))
+    first, pos = hdrio._line(buf, 0)
+    if not first.startswith(hdrio.MAGICS):
+        raise ValueError(f"{path}: missing #?RADIANCE / #?RGBE magic line")
+    raw = first
+    while raw:
+        raw, pos = hdrio._line(buf, pos)
+    res, _ = hdrio._line(buf, pos)
+    m = re.fullmatch(r"[-+]Y +(\d+) +\+X +(\d+)", res.decode("latin-1").strip())
+    if not m:
+        raise ValueError(f"{path}: bad or unsupported resolution line {res!r}")
+    return int(m.group(1)), int(m.group(2))
+
+
+def read_source(path):
+    """A picture in its file format, row 0 = top: RGBE uint8 [h,w,4] (``.hdr`` / ``.pic``, as
+    hdrio.parse_hdr returns it) or float32 [h,w,3] (``.pfm``)."""
+    if os.path.splitext(path)[1].lower() == ".pfm":
+        return np.ascontiguousarray(hdrio.read_pfm(path))
+    with open(path, "rb") as fh:
+        return hdrio.parse_hdr(fh.read())[1]
+
+
+def resize_matrix(ch, cw, h, w):
+    """S: target pixel -> window pixel, centres aligned; the identity for a window of target size."""
+    sr, sc = ch / h, cw / w
+    return np.array([[sr, 0, 0.5 * sr - 0.5], [0, sc, 0.5 * sc - 0.5], [0, 0, 1]])
+
+
+class HDRPairGenerator:
+    """The geometric arguments are ``ImageDataGenerator``'s; ``key`` / ``lum`` those of
+    ``tonemap.reinhard`` / ``tonemap.virtual_camera``."""
+
+    def __init__(self, rotation_range=0, zoom_range=0, horizontal_flip=False, vertical_flip=False, shear_range=0,
+                 width_shift_range=0, height_shift_range=0, key=0.18, lum=None, quantize="input", cameras="random"):
+        if quantize not in QUANTIZE:
+            raise ValueError(f"quantize {quantize!r}: 'input', 'both' or None")
+        if cameras not in ("random", "fixed"):
+            raise ValueError(f"cameras {cameras!r}: 'random' or 'fixed'")
+        self.geometry = ImageDataGenerator(rotation_range=rotation_range, zoom_range=zoom_range,
+                                           horizontal_flip=horizontal_flip, vertical_flip=vertical_flip,
+                                           shear_range=shear_range, width_shift_range=width_shift_range,
+                                           height_shift_range=height_shift_range)
+        self.key = float(key)
+        self.lum = None if lum is None else tuple(float(c) for c in lum)
+        self.quantize, self.cameras = quantize, cameras
+
+    def flow_from_directory(self, hdr_dir, target_size, window="random", window_size=None, batch_size=32,
+                            shuffle=True, seed=None, cache=True, workers=8, rank=None, world=None, output="cuda"):
+        """``batch_size`` is per rank; ``rank`` / ``world`` as ``ImageDataGenerator.flow_from_directory``."""
+        return HDRPairIterator(hdr_dir, self, target_size, window, window_size, batch_size, shuffle, seed, cache,
+                               workers, rank, world, output)
+
+
+class HDRPairIterator(Iterator):
+    """Yields ``(x, y)``: fp32 CUDA tensors [B, H, W, 3] (numpy arrays with ``output='numpy'``)."""
+
+    def __init__(self, hdr_dir, gen, target_size, window, window_size, batch_size, shuffle, seed, cache, workers,
+                 rank=None, world=None, output="cuda"):
+        if window not in ("random", "center", "full"):
+            raise ValueError(f"window {window!r}: 'random', 'center' or 'full'")
+        if output not in ("cuda", "numpy"):
+            raise ValueError(f"output {output!r}: 'cuda' or 'numpy'")
+        self.gen, self.target_size, self.window = gen, tuple(int(v) for v in target_size), window
+        self.window_size = self.target_size if window_size is None else tuple(int(v) for v in window_size)
+        self.cache, self.output = bool(cache), output
+        names = sorted(f for f in os.listdir(hdr_dir) if os.path.splitext(f)[1].lower() in EXTENSIONS)
+        if not names:
+            raise FileNotFoundError(f"no {'/'.join(EXTENSIONS)} files in {hdr_dir}")
+        self.filenames = [os.path.join(hdr_dir, f) for f in names]
+        self.sizes = [image_size(f) for f in self.filenames]
+        if window != "full":
+            ch, cw = self.window_size
+            for f, (hs, ws) in zip(self.filenames, self.sizes):
+                if hs < ch or ws < cw:
+                    raise ValueError(f"{f}: a {hs} x {ws} picture is smaller than the {ch} x {cw} window")
+        self.fixed_cameras = None
+        if gen.cameras == "fixed":
+            from .tonemap import virtual_camera_params
+            base = 0 if seed is None else seed
+            self.fixed_cameras = [tuple(float(a[0]) for a in virtual_camera_params(1, np.random.default_rng(base + j)))
+                                  for j in range(len(names))]
+        self._sources = {}
+        self._pool = cf.ThreadPoolExecutor(max_workers=workers)
+        self.last_draws = None
+        print(f"Found {len(names)} HDR images.")
+        super().__init__(len(names), batch_size, shuffle, seed, rank, world)
+
+    # ---- the random stream (host only) ----------------------------------------------------
+    def _draw(self, index_array):
+        """The draws of every frame of the global batch, in the documented order; returns this
+        rank's share as dicts (j, params, top, left, ch, cw, camera = (v, n, y))."""
+        h, w = self.target_size
+        rng, draws = self.rng, []
+        for j in index_array:
+            j = int(j)
+            params = self.gen.geometry.get_random_transform((h, w, 3), rng)
+            hs, ws = self.sizes[j]
+            ch, cw = (hs, ws) if self.window == "full" else self.window_size
+            if self.window == "random":
+                top = int(rng.randint(0, hs - ch + 1))
+                left = int(rng.randint(0, ws - cw + 1))
+            else:
+                top, left = (hs - ch) // 2, (ws - cw) // 2
+            if self.fixed_cameras is not None:
+                camera = self.fixed_cameras[j]
+            else:
+                v = 8 * rng.random_sample() - 4
+                n = rng.normal(0.6, np.sqrt(0.1))
+                while n <= 0:
+                    n = rng.normal(0.6, np.sqrt(0.1))
+                y = rng.normal(0.9, np.sqrt(0.1))
+                while y <= 0:
+                    y = rng.normal(0.9, np.sqrt(0.1))
+                camera = (float(v), float(n), float(y))
+            draws.append({"j": j, "params": params, "top": top, "left": left, "ch": ch, "cw": cw, "camera": camera})
+        lo, hi = self._local(len(draws))
+        return draws[lo:hi]
+
+    def next_draws(self):
+        """Advance the stream by one batch and return its draws without producing pixels."""
+        blk = next(self._gen)
+        self.last_global_batch = len(blk)
+        self.last_draws = self._draw(blk)
+        return self.last_draws
+
+    def source_matrix(self, d):
+        """(M_src [6] float64, flip bits) of one draw: output pixel -> source-picture pixel."""
+        h, w = self.target_size
+        m6, flips = ImageDataGenerator.affine(d["params"], h, w)
+        m = np.vstack([m6.reshape(2, 3), [0.0, 0.0, 1.0]])
+        t = np.array([[1, 0, d["top"]], [0, 1, d["left"]], [0, 0, 1]], np.float64)
+        m = np.dot(t, np.dot(resize_matrix(d["ch"], d["cw"], h, w), m))
+        return m[:2].reshape(-1).astype(np.float64), flips
+
+    # ---- pixels (GPU) -----------------------------------------------------------------------
+    def _load(self, js):
+        """{j: device tensor in file format}; cached files are uploaded on first use."""
+        have = self._sources if self.cache else {}
+        missing = sorted(set(js) - set(have))
+        arrays = list(self._pool.map(lambda j: read_source(self.filenames[j]), missing))
+        if missing:
+            import torch
+            for j, a in zip(missing, arrays):
+                if tuple(a.shape[:2]) != self.sizes[j]:
+                    raise ValueError(f"{self.filenames[j]}: the picture changed size since its header was read")
+                have[j] = torch.from_numpy(a).cuda()
+        return have
+
+    def _batch(self, index_array):
+        import torch
+        from . import ops
+        draws = self.last_draws = self._draw(index_array)
+        n = len(draws)
+        h, w = self.target_size
+        have = self._load([d["j"] for d in draws])
+        srcs = [have[d["j"]] for d in draws]
+        desc = ops.hdr_descriptors(srcs, [(d["top"], d["left"], d["top"] + d["ch"] - 1, d["left"] + d["cw"] - 1)
+                                          for d in draws])
+        mats, flips = zip(*[self.source_matrix(d) for d in draws])
+        cam = np.array([[self.gen.key * 2.0 ** d["camera"][0], d["camera"][1], d["camera"][2]] for d in draws],
+                       np.float64)
+        # one upload: descriptors, matrices, cameras (8-byte items), then the flips
+        parts = [desc.view(np.uint8).reshape(-1), np.stack(mats).view(np.uint8).reshape(-1),
+                 cam.view(np.uint8).reshape(-1), np.asarray(flips, np.int32).view(np.uint8)]
+        dev = torch.from_numpy(np.concatenate(parts)).cuda()
+        cuts = np.cumsum([0] + [p.size for p in parts])
+        d_desc, d_mats, d_cam, d_flips = (dev[cuts[k]:cuts[k + 1]] for k in range(4))
+        x = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev.device)
+        y = torch.empty_like(x)
+        ops.hdr_pairs(d_desc, d_mats.view(torch.float64), d_flips.view(torch.int32), d_cam.view(torch.float64), x, y,
+                      key=self.gen.key, lum=self.gen.lum, quantize=QUANTIZE[self.gen.quantize])
+        if self.output == "numpy":
+            return x.cpu().numpy(), y.cpu().numpy()
+        return x, y

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -509,3 +510,56 @@ def rgbe_decode(rgbe, rgb):
     """rgbe [...,4] uint8 -> rgb [...,3] fp32, contiguous device tensors (cnnitmo_rgbe_decode)."""
     call("cnnitmo_rgbe_decode", ptr(rgbe), _rgbe_pair(rgb, rgbe), ptr(rgb), stream_ptr())
     return rgb
+
+
+# ---------------------------------------------------------------- HDR pair generator
+# cnnitmo_hdr_src: pointer, h, w, fmt, r0, c0, r1, c1 (+ 4 bytes of tail padding)
+HDR_SRC = np.dtype({"names": ["pix", "h", "w", "fmt", "r0", "c0", "r1", "c1"],
+                    "formats": ["<u8"] + ["<i4"] * 7, "offsets": [0, 8, 12, 16, 20, 24, 28, 32], "itemsize": 40})
+
+
+def hdr_descriptors(sources, windows=None):
+    """Host array (HDR_SRC, one per output frame) for cnnitmo_hdr_pairs.  sources: contiguous device
+    tensors, fp32 [h,w,3] or RGBE uint8 [h,w,4] (the caller keeps them alive); windows: per frame the
+    inclusive clamp window (r0, c0, r1, c1), None = the whole picture.  The descriptors are read on
+    the device, so their contents are checked here."""
+    d = np.zeros(len(sources), HDR_SRC)
+    for i, t in enumerate(sources):
+        if t.ndim != 3 or not t.is_contiguous() or (t.dtype, t.shape[2]) not in ((torch.float32, 3), (torch.uint8, 4)):
+            raise ValueError(f"hdr source {i}: expected contiguous fp32 [h,w,3] or uint8 [h,w,4], got "
+                             f"{t.dtype} {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if h < 1 or w < 1:
+            raise ValueError(f"hdr source {i}: empty picture {h} x {w}")
+        win = None if windows is None else windows[i]
+        r0, c0, r1, c1 = (0, 0, h - 1, w - 1) if win is None else (int(v) for v in win)
+        if not (0 <= r0 <= r1 < h and 0 <= c0 <= c1 < w):
+            raise ValueError(f"hdr source {i}: window rows {r0}..{r1}, columns {c0}..{c1} is not inside the "
+                             f"{h} x {w} picture")
+        d[i] = (t.data_ptr(), h, w, 0 if t.dtype == torch.float32 else 1, r0, c0, r1, c1)
+    return d
+
+
+def hdr_pairs_workspace_bytes(n):
+    return int(query("cnnitmo_hdr_pairs_workspace_bytes", n))
+
+
+def hdr_pairs(srcs, mats, flips, cam, x, y, key=0.18, lum=None, quantize=0, warped=None, logsum=None, ws=None):
+    """srcs: device uint8 tensor holding n HDR_SRC descriptors (hdr_descriptors, uploaded); mats [n,6]
+    fp64, flips [n] int32, cam [n,3] fp64 device tensors; x, y (and warped) [n,h,w,3] fp32, logsum [n]
+    fp64 (cnnitmo_hdr_pairs).  lum: three host weights, None = Rec. 709."""
+    import ctypes
+    n, h, w, _ = x.shape
+    assert srcs.dtype == torch.uint8 and srcs.numel() == n * HDR_SRC.itemsize and srcs.data_ptr() % 8 == 0
+    assert mats.dtype == torch.float64 and mats.numel() == 6 * n and flips.dtype == torch.int32 and flips.numel() == n
+    assert cam.dtype == torch.float64 and cam.numel() == 3 * n
+    for t in (x, y, warped):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, h, w, 3))
+    assert logsum is None or (logsum.dtype == torch.float64 and logsum.numel() == n)
+    if ws is None:
+        ws = workspace(hdr_pairs_workspace_bytes(n), x.device)
+    lc = None if lum is None else (ctypes.c_double * 3)(*[float(c) for c in lum])
+    call("cnnitmo_hdr_pairs", ptr(srcs), n, h, w, ptr(mats), ptr(flips), None if lc is None else ctypes.addressof(lc),
+         float(key), ptr(cam), int(quantize), ptr(x), ptr(y), ptr(warped), ptr(logsum), ptr(ws), ws.numel(),
+         stream_ptr())
+    return x, y

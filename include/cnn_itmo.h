@@ -58,7 +58,8 @@ extern "C" {
 /* ABI version: 2 since CNNITMO_CONSUMER_ROWS went from 16 to 64 (a caller built against the
  * old header under-allocates cnnitmo_bn_consumer_sums' part: check cnnitmo_consumer_rows()) and
  * cnnitmo_bn_apply started to require 16-byte aligned scale / shift.  Added since without a bump
- * (new entry points only, nothing existing changed): cnnitmo_rgbe_encode / cnnitmo_rgbe_decode. */
+ * (new entry points only, nothing existing changed): cnnitmo_rgbe_encode / cnnitmo_rgbe_decode,
+ * cnnitmo_hdr_pairs / cnnitmo_hdr_pairs_workspace_bytes. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -592,6 +593,43 @@ int cnnitmo_rgb_accuracy(const float* y, const float* t, long npix, unsigned lon
  */
 int cnnitmo_rgbe_encode(const float* rgb, long npix, uint8_t* rgbe, void* stream);
 int cnnitmo_rgbe_decode(const uint8_t* rgbe, long npix, float* rgb, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Training pairs straight from HDR pictures: for each of n output frames [h][w][3] a warped
+ * window of a source picture, its Reinhard target y and its virtual-camera input x, in one call
+ * (the offline route is make_dataset's PNGs, re-decoded and warped by the data generator).
+ * srcs: DEVICE array of n descriptors; the pictures may differ in size and format.
+ *   mats / flips (device, [n][6] fp64 / [n]) as the augmentation call's, except that a
+ *   matrix maps an output (row, col), after the flips, to (row, col) of the SOURCE picture;
+ *   bilinear in fp64, the four neighbours clamped to the window [r0, r1] x [c0, c1]; an RGBE
+ *   tap is decoded by the RGBE codec's rule; the result rounded to fp32 is the warped HDR pixel
+ *   (stored to `warped` when given).
+ *   Y = lum of that pixel, fp64, no FMA contraction; logsum[i] = sum over the frame of
+ *   log(max(Y, realmin)) (stored when given), fixed partition and fixed-order fold, no atomics;
+ *   G = exp(logsum * (1 / (h*w))).
+ *   y: X = key/G * Y, L = X/(1+X), y_c = hdr_c * (L/Y);  x: the virtual-camera curve of the
+ *   tone-map call with cam (device, [n][3] = (key*2^v, n, y)).  Then NaN -> 0 (a black pixel has
+ *   Y = 0) and a clamp to [0, 1]; stored as (float)v, or for the outputs named by quantize
+ *   (bit 0: x, bit 1: y) as (float)uint8(255 v) * (float)(1/255) with imwrite's rounding.
+ * lum_coef: HOST pointer, NULL = Rec. 709.  workspace: 8-byte aligned device memory of the
+ * queried size, contents irrelevant.  The window must lie inside the picture and fmt be 0 or 1:
+ * the descriptors live on the device, so the caller checks that (ops.hdr_descriptors does); the
+ * kernels cut the window to the picture.  An RGBE picture that is not 4-byte aligned is read by
+ * bytes.  CNNITMO_EINVAL before any device call: a null pointer (warped and logsum may be
+ * null), n, h or w <= 0, n > 65535, h*w >= 2^31, quantize outside 0..3, a short or misaligned
+ * workspace.
+ */
+typedef struct {
+  const void* pix; /* source picture, row 0 = top (device) */
+  int h, w;        /* its size */
+  int fmt;         /* 0: fp32 RGB [h][w][3]   1: RGBE bytes [h][w][4] */
+  int r0, c0, r1, c1; /* inclusive clamp window inside the picture */
+} cnnitmo_hdr_src;
+
+size_t cnnitmo_hdr_pairs_workspace_bytes(int n);
+int cnnitmo_hdr_pairs(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats, const int* flips,
+                      const double* lum_coef, double key, const double* cam, int quantize, float* x, float* y,
+                      float* warped, double* logsum, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
