@@ -1,0 +1,125 @@
+"""Score a directory of HDR reconstructions against their HDR references (hdrmetrics.py).
+
+    python -m cnn_itmo_amd.evaluate_hdr --pred DIR --reference DIR [--encoding pq|log] \\
+        [--align logmean|median|none] [--anchor key|percentile|FLOAT] [--key 0.18] \\
+        [--white-nits 203] [--percentile 0.999] [--peak-nits 1000] [--csv FILE]
+
+Every ``.hdr`` / ``.pic`` / ``.pfm`` file of ``--pred`` (sorted) is paired with the file of the
+same stem in ``--reference`` (any of the three extensions), both are read with
+``hdrio.read_image``, aligned, anchored to cd/m^2 and encoded, and PSNR / SSIM of the encoded
+pair are printed per file and as the mean.  A missing reference is reported and skipped, a size
+mismatch is an error (as ``predict --reference``).  ``--csv``: also write
+``name;psnr;ssim;scale_pred;scale_ref`` rows.  ``predict --hdr DIR --hdr-reference DIR`` scores
+the reconstructions it wrote with the same functions.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+EXTENSIONS = (".hdr", ".pic", ".pfm")
+CSV_HEADER = "name;psnr;ssim;scale_pred;scale_ref"
+
+
+def hdr_files(directory):
+    """The HDR image files of a directory, sorted by name."""
+    return sorted(os.path.join(directory, f) for f in os.listdir(directory)
+                  if os.path.splitext(f)[1].lower() in EXTENSIONS)
+
+
+def find_reference(ref_dir, stem):
+    """The file ``stem`` + one of EXTENSIONS in ref_dir (either letter case), or None."""
+    for ext in EXTENSIONS:
+        for e in (ext, ext.upper()):
+            p = os.path.join(ref_dir, stem + e)
+            if os.path.exists(p):
+                return p
+    return None
+
+
+def score_files(pred_path, ref_path, encoding="pq", **opts):
+    """(psnr dB, ssim, scale_pred, scale_ref) of the HDR file pred_path against ref_path, both read
+    from disk; ``opts``: hdrmetrics.hdr_scales' keywords."""
+    from . import hdrio, hdrmetrics, ops
+    p, r = hdrio.read_image(pred_path), hdrio.read_image(ref_path)
+    if p.shape != r.shape:
+        raise ValueError(f"{ref_path}: reference is {r.shape[1]}x{r.shape[0]}, the prediction "
+                         f"{os.path.basename(pred_path)} {p.shape[1]}x{p.shape[0]}")
+    out, sp, sr = hdrmetrics._score(ops.MSE_PSNR | ops.SSIM, p, r, encoding, **opts)
+    return float(out[0, 1].item()), float(out[0, 2].item()), float(sp.item()), float(sr.item())
+
+
+def log_score(log, name, score):
+    ps, ss, sp, sr = score
+    log(f"{name}: hdr psnr {ps:.4f} dB, ssim {ss:.6f} (scale_pred {sp:.6g}, scale_ref {sr:.6g})")
+
+
+def log_mean(log, scores):
+    if scores:
+        log(f"mean of {len(scores)} scored HDR files: psnr {np.mean([s[1] for s in scores]):.4f} dB, "
+            f"ssim {np.mean([s[2] for s in scores]):.6f}")
+
+
+def write_csv(path, scores):
+    """scores: (name, psnr, ssim, scale_pred, scale_ref) tuples."""
+    with open(path, "w", newline="") as fh:
+        fh.write(CSV_HEADER + "\n")
+        for name, ps, ss, sp, sr in scores:
+            fh.write(f"{name};{ps:.10g};{ss:.10g};{sp:.17g};{sr:.17g}\n")
+
+
+def evaluate_dir(pred_dir, ref_dir, csv=None, log=print, encoding="pq", **opts):
+    """Score every HDR file of pred_dir; returns the (name, psnr, ssim, scale_pred, scale_ref) rows."""
+    files = hdr_files(pred_dir)
+    if not files:
+        raise FileNotFoundError(f"no {'/'.join(EXTENSIONS)} files in {pred_dir}")
+    scores = []
+    for f in files:
+        name = os.path.basename(f)
+        ref = find_reference(ref_dir, os.path.splitext(name)[0])
+        if ref is None:
+            log(f"{name}: no reference in {ref_dir}, not scored")
+            continue
+        score = score_files(f, ref, encoding=encoding, **opts)
+        log_score(log, name, score)
+        scores.append((name,) + tuple(score))
+    log_mean(log, scores)
+    if csv:
+        write_csv(csv, scores)
+    return scores
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--pred", required=True, help="directory of HDR reconstructions (.hdr / .pic / .pfm)")
+    ap.add_argument("--reference", required=True, help="directory of ground-truth HDR files, paired by stem")
+    ap.add_argument("--encoding", default="pq", choices=["pq", "log"])
+    ap.add_argument("--align", default="logmean", choices=["logmean", "median", "none"],
+                    help="the scale that aligns a reconstruction to its reference")
+    ap.add_argument("--anchor", default="key",
+                    help="key, percentile, or a number: cd/m^2 per unit of the reference (calibrated files)")
+    ap.add_argument("--key", type=float, default=0.18, help="anchor key: the key placed on --white-nits")
+    ap.add_argument("--white-nits", type=float, default=203.0)
+    ap.add_argument("--percentile", type=float, default=0.999,
+                    help="anchor percentile: the luminance percentile placed on --peak-nits")
+    ap.add_argument("--peak-nits", type=float, default=1000.0)
+    ap.add_argument("--csv", default=None, help=f"write {CSV_HEADER} rows to this file")
+    a = ap.parse_args(argv)
+    from . import hdrmetrics
+    try:
+        anchor = hdrmetrics._anchor(a.anchor)
+    except ValueError as e:
+        ap.error(str(e))
+    if not 0.0 < a.percentile <= 1.0:
+        ap.error(f"--percentile {a.percentile} outside (0, 1]")
+    scores = evaluate_dir(a.pred, a.reference, csv=a.csv, encoding=a.encoding, align=a.align, anchor=anchor,
+                          key=a.key, white_nits=a.white_nits, q=a.percentile, peak_nits=a.peak_nits)
+    print(f"scored {len(scores)} of {len(hdr_files(a.pred))} files of {a.pred}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -563,3 +563,40 @@ def hdr_pairs(srcs, mats, flips, cam, x, y, key=0.18, lum=None, quantize=0, warp
          float(key), ptr(cam), int(quantize), ptr(x), ptr(y), ptr(warped), ptr(logsum), ptr(ws), ws.numel(),
          stream_ptr())
     return x, y
+
+
+# ---------------------------------------------------------------- HDR quality metrics
+HDR_ENCODINGS = {"pq": 0, "log": 1}  # CNNITMO_ENC_*
+
+
+def hdr_encode(encoding, img, scale, out=None):
+    """img [n,h,w,3] contiguous fp32, scale [n] fp64 device tensors -> out like img: the PQ / log
+    encoding of img * scale (cnnitmo_hdr_encode).  encoding: an HDR_ENCODINGS id."""
+    n, h, w, c = img.shape
+    assert c == 3 and img.dtype == torch.float32 and img.is_contiguous(), (img.dtype, tuple(img.shape))
+    assert scale.dtype == torch.float64 and scale.is_contiguous() and scale.numel() == n
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
+    call("cnnitmo_hdr_encode", int(encoding), ptr(img), n, h, w, ptr(scale), ptr(out), stream_ptr())
+    return out
+
+
+def lum_percentile_workspace_bytes(n):
+    return int(query("cnnitmo_lum_percentile_workspace_bytes", n))
+
+
+def lum_percentile(img, q, lum=None, out=None):
+    """img [n,h,w,3] contiguous fp32 device tensor -> out [n] fp32: the histogram percentile Q_q of
+    each image's luminance (cnnitmo_lum_percentile).  lum: three host weights, None = Rec. 709."""
+    import ctypes
+    n, h, w, c = img.shape
+    assert c == 3 and img.dtype == torch.float32 and img.is_contiguous(), (img.dtype, tuple(img.shape))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=img.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n
+    ws = workspace(lum_percentile_workspace_bytes(n), img.device)
+    lc = None if lum is None else (ctypes.c_double * 3)(*[float(c) for c in lum])
+    call("cnnitmo_lum_percentile", ptr(img), n, h, w, None if lc is None else ctypes.addressof(lc), float(q),
+         ptr(out), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out

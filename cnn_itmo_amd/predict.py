@@ -12,7 +12,8 @@ Here the same conventions run batched on the GPU:
         [--input images_to_predict/input] [--output images_to_predict/output] \\
         [--batch 8] [--dtype float32|bfloat16] [--tile TH,TW] \\
         [--reference ground_truth_dir [--metrics-csv scores.csv]] \\
-        [--hdr DIR [--hdr-format hdr|pfm] [--hdr-mode script|exact] [--hdr-key A] [--hdr-log-average G]]
+        [--hdr DIR [--hdr-format hdr|pfm] [--hdr-mode script|exact] [--hdr-key A] \\
+         [--hdr-log-average G|reference] [--hdr-reference hdr_ground_truth_dir [--hdr-metrics-csv scores.csv]]]
 
 Differences, all deliberate: images are processed in sorted order, in batches
 of equal-sized frames; the output file name is the input's base name (the
@@ -136,9 +137,15 @@ def write_hdr_prediction(path, pred_u8, pred_f32=None, mode="script", key=0.18, 
     hdrio.write_image(path, hdr[0])
 
 
+def reference_log_average(ref_path):
+    """The log-average luminance of the HDR file ref_path (``--hdr-log-average reference``)."""
+    from . import hdrio, tonemap
+    return float(tonemap.log_average(hdrio.read_image(ref_path)).item())
+
+
 def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None, reference=None,
                 metrics_csv=None, hdr_dir=None, hdr_format="hdr", hdr_mode="script", hdr_key=0.18,
-                hdr_log_average=1.0):
+                hdr_log_average=1.0, hdr_reference=None, hdr_metrics_csv=None):
     """``reference``: a directory of ground-truth PNGs; every written prediction is scored
     against the file of the same name there (PSNR / SSIM, logged per file and as the mean; a
     missing reference is reported and skipped, a size mismatch raises).  ``metrics_csv``:
@@ -146,12 +153,26 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
     ``hdr_dir``: also write every prediction's HDR reconstruction there as ``name.hdr`` (Radiance
     RGBE) or ``name.pfm`` (``hdr_format``); ``hdr_mode`` 'script' applies inverse_Reinhard.m to
     the written 8-bit prediction, 'exact' the exact inverse of Reinhard.m (key ``hdr_key``,
-    log-average ``hdr_log_average``) to the float prediction.  The PNGs are the same either way."""
+    log-average ``hdr_log_average``) to the float prediction.  The PNGs are the same either way.
+    ``hdr_reference``: a directory of ground-truth HDR files (.hdr / .pic / .pfm); every
+    reconstruction written to ``hdr_dir`` is read back from disk and scored against the file of the
+    same stem there (hdrmetrics.hdr_psnr_ssim with its defaults; logged per file and as the mean, a
+    missing reference reported and skipped, a size mismatch raises).  ``hdr_metrics_csv``: also
+    write ``name;psnr;ssim;scale_pred;scale_ref`` rows.  ``hdr_log_average='reference'`` ('exact'
+    mode, with ``hdr_reference``): each file's log-average is that of its reference."""
     from PIL import Image
+    from . import evaluate_hdr as EH
     if hdr_format not in ("hdr", "pfm"):
         raise ValueError(f"hdr format {hdr_format!r} (hdr or pfm)")
     if hdr_mode not in ("script", "exact"):
         raise ValueError(f"hdr mode {hdr_mode!r} (script or exact)")
+    if hdr_reference is not None and hdr_dir is None:
+        raise ValueError("hdr_reference needs hdr_dir: the reconstructions written there are what is scored")
+    if hdr_metrics_csv and hdr_reference is None:
+        raise ValueError("hdr_metrics_csv needs hdr_reference")
+    from_reference = hdr_log_average == "reference"
+    if from_reference and (hdr_reference is None or hdr_mode != "exact"):
+        raise ValueError("hdr_log_average='reference' needs hdr_mode='exact' and hdr_reference")
     files = sorted(glob.glob(os.path.join(in_dir, pattern)))
     if not files:
         raise FileNotFoundError(f"no {pattern} files in {in_dir}")
@@ -166,6 +187,7 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
     cache = {}
     written = []
     scores = []
+    hdr_scores = []
     for shape, fs in groups.items():
         log(f"Grabbing {len(fs)} input files of {shape[1]}x{shape[0]}")
         preds = predict_frames(model, [frames[f] for f in fs], batch, cache, tile, return_float=want_float)
@@ -176,8 +198,20 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
             written.append(dst)
             if hdr_dir is not None:
                 stem = os.path.splitext(os.path.basename(f))[0]
-                write_hdr_prediction(os.path.join(hdr_dir, f"{stem}.{hdr_format}"), p, pf, hdr_mode, hdr_key,
-                                     hdr_log_average)
+                hdr_dst = os.path.join(hdr_dir, f"{stem}.{hdr_format}")
+                hdr_ref = None if hdr_reference is None else EH.find_reference(hdr_reference, stem)
+                if from_reference and hdr_ref is None:
+                    raise FileNotFoundError(f"{os.path.basename(f)}: no reference {stem}.hdr/.pic/.pfm in "
+                                            f"{hdr_reference} to take the log-average from")
+                g = reference_log_average(hdr_ref) if from_reference else hdr_log_average
+                write_hdr_prediction(hdr_dst, p, pf, hdr_mode, hdr_key, g)
+                if hdr_reference is not None:
+                    if hdr_ref is None:
+                        log(f"{os.path.basename(hdr_dst)}: no reference in {hdr_reference}, not scored")
+                    else:
+                        score = EH.score_files(hdr_dst, hdr_ref)
+                        EH.log_score(log, os.path.basename(hdr_dst), score)
+                        hdr_scores.append((os.path.basename(hdr_dst),) + tuple(score))
             if reference is not None:
                 ref = os.path.join(reference, os.path.basename(f))
                 if not os.path.exists(ref):
@@ -195,7 +229,16 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
                 fh.write("name;psnr;ssim\n")
                 for name, ps, ss in scores:
                     fh.write(f"{name};{ps:.10g};{ss:.10g}\n")
+    if hdr_reference is not None:
+        EH.log_mean(log, hdr_scores)
+        if hdr_metrics_csv:
+            EH.write_csv(hdr_metrics_csv, hdr_scores)
     return written
+
+
+def _log_average_arg(s):
+    """--hdr-log-average: a float, or the word 'reference'."""
+    return "reference" if s == "reference" else float(s)
 
 
 def main(argv=None):
@@ -218,11 +261,23 @@ def main(argv=None):
                     help="script: inverse_Reinhard.m on the written 8-bit PNG; exact: the exact inverse of "
                          "Reinhard.m on the float prediction (no banding)")
     ap.add_argument("--hdr-key", type=float, default=0.18, help="the Reinhard key a")
-    ap.add_argument("--hdr-log-average", type=float, default=1.0,
-                    help="exact mode: the log-average luminance of the HDR image to reconstruct")
+    ap.add_argument("--hdr-log-average", type=_log_average_arg, default=1.0, metavar="G|reference",
+                    help="exact mode: the log-average luminance of the HDR image to reconstruct; 'reference' "
+                         "(with --hdr-reference): that of each file's reference")
+    ap.add_argument("--hdr-reference", default=None, metavar="DIR",
+                    help="with --hdr: directory of ground-truth HDR files (.hdr / .pic / .pfm); score each "
+                         "written reconstruction against the same-stem file (PQ PSNR and SSIM, hdrmetrics)")
+    ap.add_argument("--hdr-metrics-csv", default=None,
+                    help="with --hdr-reference: write name;psnr;ssim;scale_pred;scale_ref rows to this file")
     a = ap.parse_args(argv)
     if a.metrics_csv and not a.reference:
         ap.error("--metrics-csv needs --reference")
+    if a.hdr_reference and not a.hdr:
+        ap.error("--hdr-reference needs --hdr")
+    if a.hdr_metrics_csv and not a.hdr_reference:
+        ap.error("--hdr-metrics-csv needs --hdr-reference")
+    if a.hdr_log_average == "reference" and not (a.hdr_reference and a.hdr_mode == "exact"):
+        ap.error("--hdr-log-average reference needs --hdr-mode exact and --hdr-reference")
     tile = tuple(int(v) for v in a.tile.split(",")) if a.tile else None
     from .model import load_model
     m = load_model(a.model)
@@ -231,7 +286,8 @@ def main(argv=None):
     m.set_dtype(a.dtype)
     out = predict_dir(m, a.input, a.output, a.batch, tile=tile, reference=a.reference, metrics_csv=a.metrics_csv,
                       hdr_dir=a.hdr, hdr_format=a.hdr_format, hdr_mode=a.hdr_mode, hdr_key=a.hdr_key,
-                      hdr_log_average=a.hdr_log_average)
+                      hdr_log_average=a.hdr_log_average, hdr_reference=a.hdr_reference,
+                      hdr_metrics_csv=a.hdr_metrics_csv)
     print(f"wrote {len(out)} predictions to {a.output}")
     if a.hdr:
         print(f"wrote {len(out)} .{a.hdr_format} reconstructions to {a.hdr}")

@@ -59,7 +59,8 @@ extern "C" {
  * old header under-allocates cnnitmo_bn_consumer_sums' part: check cnnitmo_consumer_rows()) and
  * cnnitmo_bn_apply started to require 16-byte aligned scale / shift.  Added since without a bump
  * (new entry points only, nothing existing changed): cnnitmo_rgbe_encode / cnnitmo_rgbe_decode,
- * cnnitmo_hdr_pairs / cnnitmo_hdr_pairs_workspace_bytes. */
+ * cnnitmo_hdr_pairs / cnnitmo_hdr_pairs_workspace_bytes, cnnitmo_hdr_encode,
+ * cnnitmo_lum_percentile / cnnitmo_lum_percentile_workspace_bytes. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -630,6 +631,43 @@ size_t cnnitmo_hdr_pairs_workspace_bytes(int n);
 int cnnitmo_hdr_pairs(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats, const int* flips,
                       const double* lum_coef, double key, const double* cam, int quantize, float* x, float* y,
                       float* warped, double* logsum, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * HDR quality metrics: the maps that put two linear-radiance images (fp32 [n][h][w][3],
+ * contiguous) in front of cnnitmo_image_metrics (max_val 1).  fp64, no FMA contraction.
+ *
+ * cnnitmo_hdr_encode: out = (float)E(x), x = (double)v * scale[i] for every channel value v of
+ * image i; scale: DEVICE double [n], cd/m^2 per unit.
+ *   CNNITMO_ENC_PQ  (SMPTE ST 2084): L = fmin(fmax(x, 0), 1e4), y = L / 1e4,
+ *                   E = pow((c1 + c2 y^m1) / (1 + c3 y^m1), m2), m1 = 2610/16384,
+ *                   m2 = 2523/4096*128, c1 = 3424/4096, c2 = 2413/4096*32, c3 = 2392/4096*32;
+ *   CNNITMO_ENC_LOG L = fmin(fmax(x, 0.005), 1e4), E = (log10 L - log10 0.005) / (4 - log10 0.005).
+ *   NaN and negative x encode like the bottom of the range, +inf like 1e4 (C fmax / fmin).
+ * 16-byte accesses when 3*h*w % 4 == 0 and img, out are 16-byte aligned, one value per thread
+ * otherwise: the same values.  Every element of out is written exactly once; out may not alias img.
+ *
+ * cnnitmo_lum_percentile: out[i] (device float [n]) = Q_q of the luminance Y of image i
+ * (lum_coef: HOST pointer to 3 weights, NULL = Rec. 709), defined on the bits of (float)Y:
+ *   bin = (bits >> 17) - (bits(2^-32f) >> 17), 4096 bins = 64 octaves x 64; below 2^-32, zero,
+ *   negatives and NaN -> bin 0; >= 2^32 -> bin 4095; need = max(1, ceil(q*h*w)) in double;
+ *   b = the first bin whose cumulative count reaches need; Q = the float with the bits
+ *   (b + 1 + (bits(2^-32f) >> 17)) << 17, the upper edge of b.
+ * So Q >= the order statistic of rank need, by less than a factor 1 + 1/64.  Integer counts
+ * (LDS histogram per workgroup, integer atomics into the workspace): bitwise reproducible.
+ * workspace: cnnitmo_lum_percentile_workspace_bytes(n) bytes of device memory, 4-byte aligned,
+ * contents irrelevant (the call zeroes it); the query needs no GPU, <= 0 for n <= 0.
+ *
+ * CNNITMO_EINVAL before any device call: a null pointer (lum_coef may be null), an unknown
+ * encoding, n, h or w <= 0, n > 65535 or h*w >= 2^31 (percentile), q outside (0, 1], a misaligned
+ * pointer, a short workspace.
+ */
+#define CNNITMO_ENC_PQ 0
+#define CNNITMO_ENC_LOG 1
+int cnnitmo_hdr_encode(int encoding, const float* img, int n, int h, int w, const double* scale, float* out,
+                       void* stream);
+long cnnitmo_lum_percentile_workspace_bytes(int n);
+int cnnitmo_lum_percentile(const float* img, int n, int h, int w, const double* lum_coef, double q, float* out,
+                           void* workspace, long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
