@@ -10,11 +10,13 @@ from .model import Model, load_model
 from .optimizers import SGD, Adam, RMSprop
 from .losses import DSSIM
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
-from .callbacks import CSVLogger, LambdaCallback, ModelCheckpoint
+from .callbacks import (CSVLogger, EarlyStopping, LambdaCallback, LearningRateScheduler, ModelCheckpoint,
+                        ReduceLROnPlateau, TerminateOnNaN)
 from . import hdrio, hdrmetrics, metrics
 from .hdrgen import HDRPairGenerator, HDRPairIterator
 
 __all__ = ["HDRPairGenerator", "HDRPairIterator","Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
            "Adam", "SGD", "DSSIM", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
-           "LambdaCallback", "ModelCheckpoint", "metrics", "hdrio", "hdrmetrics"]
+           "LambdaCallback", "ModelCheckpoint", "LearningRateScheduler", "ReduceLROnPlateau", "EarlyStopping",
+           "TerminateOnNaN", "metrics", "hdrio", "hdrmetrics"]

@@ -130,6 +130,9 @@ SIGNATURES = {
     "cnnitmo_rgb_accuracy": (i32, [vp, vp, i64, vp, vp]),
     "cnnitmo_adam": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),
+    "cnnitmo_grad_sumsq_workspace_bytes": (i64, [i64]),
+    "cnnitmo_grad_sumsq": (i32, [vp, i64, vp, vp, vp]),
+    "cnnitmo_grad_clip": (i32, [vp, i64, vp, f64, f64, f64, vp]),
     "cnnitmo_rgbe_encode": (i32, [vp, i64, vp, vp]),
     "cnnitmo_rgbe_decode": (i32, [vp, i64, vp, vp]),
     "cnnitmo_hdr_pairs_workspace_bytes": (sz, [i32]),

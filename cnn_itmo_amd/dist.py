@@ -174,6 +174,14 @@ def broadcast_state(engine, src=0, group=None):
     engine.weights_dirty = True
 
 
+def broadcast_weights(engine, src=0, group=None):
+    """Every rank takes rank `src`'s parameters and moving statistics (the optimizer state and
+    the counters stay: they are the same on every rank already)."""
+    for t in (engine.params, engine.bufs):
+        dist.broadcast(t, src, group=group)
+    engine.weights_dirty = True
+
+
 def attach(engine, bucket_mb=16.0, group=None, broadcast=True):
     """Wire a GradBucketer into an Engine; returns it.  Use
     ``engine.train_step(..., sync=b.finish, grad_scale=b.grad_scale)``."""

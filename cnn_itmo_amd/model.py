@@ -105,6 +105,7 @@ class Model:
         self._dp_args = None
         self.dtype = "float32"
         self.stop_training = False
+        self._weights_set = 0    # set_named_weights calls (fit_generator: did a callback set weights?)
         self._init_weights(kwargs.get("seed", 0))
 
     # ---- weights -------------------------------------------------------------
@@ -127,6 +128,7 @@ class Model:
         return {k: v.copy() for k, v in self._weights.items()}
 
     def set_named_weights(self, named):
+        self._weights_set += 1
         for k, v in named.items():
             if k not in self._weights:
                 raise KeyError(k)
@@ -422,7 +424,10 @@ class Model:
         gradients under data parallelism (see train_on_batch).  ``distributed=True`` (or None with an initialised process group
         of more than one rank) trains data-parallel: each rank consumes its own
         generator, logs are averaged over all ranks' samples, callbacks run on rank 0
-        only and a ``stop_training`` raised there stops every rank."""
+        only and a ``stop_training`` raised there stops every rank; every rank takes rank 0's
+        ``optimizer.lr`` after on_epoch_begin and on_epoch_end (LearningRateScheduler,
+        ReduceLROnPlateau), and rank 0's weights after on_train_end when a callback set them.
+        Keys a callback adds to the epoch logs ('lr') reach ``History.history`` too."""
         self._check_compiled()
         if distributed or (distributed is None and self._dp is None and _dist_world() > 1):
             self.distribute()
@@ -431,9 +436,18 @@ class Model:
         cbs = CallbackList((callbacks or []) if rank == 0 else [], self)
         hist = History()
         self.stop_training = False
+        weights_set = self._weights_set
+
+        def sync_lr():
+            # callbacks run on rank 0 only: every rank takes rank 0's learning rate (exact: one
+            # non-zero term in a float64 sum), or an LR callback would desynchronise the replicas
+            if world > 1:
+                self.optimizer.lr = float(self._allreduce_sum([self.optimizer.lr if rank == 0 else 0.0])[0])
+
         cbs.call("on_train_begin", {})
         for epoch in range(initial_epoch, epochs):
             cbs.call("on_epoch_begin", epoch, {})
+            sync_lr()
             t0 = time.time()
             pending = []
             for step in range(steps_per_epoch):
@@ -456,12 +470,21 @@ class Model:
             hist.epoch.append(epoch)
             for k, v in logs.items():
                 hist.history.setdefault(k, []).append(v)
+            own = set(logs)
             cbs.call("on_epoch_end", epoch, logs)
+            for k, v in logs.items():  # keys a callback added ('lr'): Keras' History runs last
+                if k not in own:
+                    hist.history.setdefault(k, []).append(v)
+            sync_lr()
             if world > 1:
                 self.stop_training = bool(self._allreduce_sum([float(self.stop_training)])[0])
             if self.stop_training:
                 break
         cbs.call("on_train_end", {})
+        if world > 1 and self._allreduce_sum([float(self._weights_set != weights_set)])[0]:
+            # a callback set weights on rank 0 (EarlyStopping(restore_best_weights=True))
+            from . import dist as D
+            D.broadcast_weights(self._engine(), group=self._dp_args[1])
         return hist
 
     # ---- summary -------------------------------------------------------------------

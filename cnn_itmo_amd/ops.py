@@ -428,6 +428,35 @@ def sgd(p, g, mom, lr, momentum=0.0, nesterov=False, grad_scale=1.0):
          stream_ptr())
 
 
+def grad_sumsq_workspace_bytes(n):
+    return int(query("cnnitmo_grad_sumsq_workspace_bytes", n))
+
+
+def grad_sumsq(g, out=None, ws=None):
+    """g: contiguous 1-D fp32 device tensor -> out (float64 [1], device) = sum g^2 in fp64, bitwise
+    reproducible (cnnitmo_grad_sumsq).  ws: a uint8 workspace of grad_sumsq_workspace_bytes(n)."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 1, (g.dtype, tuple(g.shape))
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=g.device)
+    assert out.dtype == torch.float64 and out.numel() >= 1
+    if ws is None:
+        ws = workspace(grad_sumsq_workspace_bytes(g.numel()), g.device)
+    assert ws.numel() * ws.element_size() >= grad_sumsq_workspace_bytes(g.numel())
+    call("cnnitmo_grad_sumsq", ptr(g), g.numel(), ws.data_ptr(), ptr(out), stream_ptr())
+    return out
+
+
+def grad_clip(g, sumsq, grad_scale=1.0, clipnorm=0.0, clipvalue=0.0):
+    """In place on g (contiguous 1-D fp32): Keras' clipnorm (global norm, from sumsq = grad_sumsq(g),
+    read on the device) then clipvalue, of the gradient g * grad_scale (cnnitmo_grad_clip).  sumsq
+    may be None without clipnorm."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 1, (g.dtype, tuple(g.shape))
+    assert sumsq is None or sumsq.dtype == torch.float64
+    call("cnnitmo_grad_clip", ptr(g), g.numel(), ptr(sumsq), float(grad_scale), float(clipnorm or 0.0),
+         float(clipvalue or 0.0), stream_ptr())
+    return g
+
+
 def augment_affine(src, mats, flips, scale, dst):
     """src [n,h,w,c] uint8/fp32 device tensor; mats [n,6] fp64 and flips [n] int32 device
     tensors; dst [n,h,w,c] fp32 (cnnitmo_augment_affine)."""

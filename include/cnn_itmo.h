@@ -60,7 +60,8 @@ extern "C" {
  * cnnitmo_bn_apply started to require 16-byte aligned scale / shift.  Added since without a bump
  * (new entry points only, nothing existing changed): cnnitmo_rgbe_encode / cnnitmo_rgbe_decode,
  * cnnitmo_hdr_pairs / cnnitmo_hdr_pairs_workspace_bytes, cnnitmo_hdr_encode,
- * cnnitmo_lum_percentile / cnnitmo_lum_percentile_workspace_bytes. */
+ * cnnitmo_lum_percentile / cnnitmo_lum_percentile_workspace_bytes,
+ * cnnitmo_grad_sumsq / cnnitmo_grad_sumsq_workspace_bytes / cnnitmo_grad_clip. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -489,6 +490,38 @@ int cnnitmo_adam(float* p, const float* g, float* m, float* v, long n, float lr_
                  float eps, float grad_scale, void* stream);
 int cnnitmo_sgd(float* p, const float* g, float* mom, long n, float lr, float momentum, int nesterov,
                 float grad_scale, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Gradient clipping (keras.optimizers clipnorm / clipvalue, Keras 2.2 get_gradients: by the
+ * GLOBAL norm over all gradients, then by value), over the flat fp32 gradient buffer, before
+ * the update kernels above.  Nothing here waits for the host.
+ *
+ * cnnitmo_grad_sumsq: out[0] (device double) = sum g[i]^2, accumulated in fp64 (each square is
+ *   exact, only the additions round: relative error <= n * 2^-53).  Bitwise reproducible: the
+ *   grid and every thread's element order depend on n alone, workgroup partials go to the
+ *   workspace and a second one-workgroup launch adds them in a fixed order; no atomics.  An
+ *   aligned and a misaligned buffer holding the same values give the same bits.
+ *   workspace: cnnitmo_grad_sumsq_workspace_bytes(n) bytes of device memory, 8-byte aligned,
+ *   contents irrelevant; the query needs no GPU, 0 for n <= 0.
+ * cnnitmo_grad_clip: in place; S = sumsq[0] is read on the device.  grad_scale is the factor the
+ *   update kernel will apply to g (1 / world under data parallelism), so that the clipped
+ *   quantity is the averaged gradient g' = g * grad_scale:
+ *     N = grad_scale * sqrt(S) in fp64;
+ *     f = clipnorm / N  if clipnorm > 0, S is finite and N >= clipnorm;  f = 1 otherwise;
+ *     v = (float)((double)g[i] * f);
+ *     if clipvalue > 0:  b = (float)(clipvalue / grad_scale),  v = min(max(v, -b), b)
+ *     (by comparisons: a NaN stays a NaN).
+ *   clipnorm <= 0 switches norm clipping off (sumsq may then be NULL), clipvalue <= 0 value
+ *   clipping; both off is an argument error.
+ * g must be 4-byte aligned: 16-byte accesses when it is 16-byte aligned, dword accesses
+ * otherwise and for the tail; the values are the same either way.  CNNITMO_EINVAL before any
+ * device call: a null or misaligned pointer, n <= 0, grad_scale not positive and finite, a NaN
+ * clipnorm / clipvalue, clipnorm > 0 without sumsq.
+ */
+long cnnitmo_grad_sumsq_workspace_bytes(long n);
+int cnnitmo_grad_sumsq(const float* g, long n, void* workspace, double* out, void* stream);
+int cnnitmo_grad_clip(float* g, long n, const double* sumsq, double grad_scale, double clipnorm, double clipvalue,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------
  * Training-data augmentation -- replaces the paired keras ImageDataGenerator
