@@ -127,6 +127,8 @@ SIGNATURES = {
     "cnnitmo_head_fwd_bwd_given": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "cnnitmo_dssim_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "cnnitmo_dssim_loss_grad": (i32, [i32, f64, vp, vp, i32, i32, i32, f64, vp, vp, vp, i64, vp]),
+    "cnnitmo_msssim_workspace_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "cnnitmo_msssim_loss_grad": (i32, [i32, f64, vp, i32, f64, vp, vp, i32, i32, i32, f64, vp, vp, vp, i64, vp]),
     "cnnitmo_rgb_accuracy": (i32, [vp, vp, i64, vp, vp]),
     "cnnitmo_adam": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),

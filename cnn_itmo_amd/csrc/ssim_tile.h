@@ -1,8 +1,11 @@
-// The SSIM tile pass shared by the image metrics (metrics.hip: ssim_mse_kernel) and the DSSIM
-// training loss (dssim.hip: dssim_coef_kernel): one workgroup owns TR x TC positions of the
-// SSIM map of an NHWC RGB image addressed in float columns (see metrics.hip for the layout,
-// the numerics and the reduction).  Include it after `#pragma clang fp contract(off)`: only
-// the filter taps accumulate with (explicit) fma().
+// The SSIM tile pass shared by the image metrics (metrics.hip: ssim_mse_kernel), the DSSIM
+// training loss (dssim.hip: dssim_coef_kernel) and the multi-scale loss (msssim.hip:
+// msssim_coef_kernel): one workgroup owns TR x TC positions of the SSIM map of an NHWC RGB image
+// addressed in float columns (see metrics.hip for the layout, the numerics and the reduction).
+// adjoint_pass is the other direction, the full correlation of the coefficient planes with the
+// window, as msssim_grad_kernel runs it per level (dssim_grad_kernel keeps its own copy of that
+// loop, so that it compiles to what it did before the multi-scale loss).  Include this file
+// after `#pragma clang fp contract(off)`: only the filter taps accumulate with (explicit) fma().
 #pragma once
 #include <math.h>
 
@@ -83,14 +86,25 @@ __device__ __forceinline__ double element_term(int base, double d) {
 // part [n][nblk][2] = (sum of the SSIM term, sum of the element term) of a tile.
 // MODE == BASE_TERM_AND_PLANES: planes [n][3][mh][mw3] fp64 = (Pa, Pb, Pc) of every map element
 // (dssim.hip), a the prediction and b the target.  base: a CNNITMO_BASE_* (unused in SQUARED_ERROR).
-template <bool VEC, int MODE>
-__device__ __forceinline__ void tile_pass(const float* __restrict__ a, const float* __restrict__ b, int h, int w,
+// The multi-scale loss (msssim.hip) adds: T = double, a pyramid level (scalar staging only);
+// PER_CHANNEL, part [n][nblk][4] = (the term's sum over the R, G, B columns, the element term's
+// sum): a float column's channel is column % 3 and TC is a multiple of 3; CS_ONLY, the term is
+// the contrast-structure factor cs = A2 / B2 and the planes are those of S with A1 = B1 = 1.
+template <bool VEC, int MODE, typename T = float, bool PER_CHANNEL = false, bool CS_ONLY = false>
+__device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __restrict__ b, int h, int w,
                                           int base, Taps tp, double c1, double c2,
                                           double* __restrict__ part, double* __restrict__ planes) {
-  __shared__ float sa[IR][ICP];
-  __shared__ float sb[IR][ICP];
-  __shared__ double hs[5][IR][TC];
-  __shared__ double red[NT / 64][2];
+  static_assert(!VEC || sizeof(T) == sizeof(float), "the 16-byte staging path is fp32's");
+  static_assert(TC % 3 == 0, "a tile's first float column is a red one");
+  // fp64 input doubles the staged windows; to stay at two workgroups per CU (80 KB each) the row
+  // sums of yy and xy then take the windows' place once the horizontal pass has read them
+  constexpr bool ALIAS = sizeof(T) == sizeof(double);
+  constexpr int HI = (IR * (TC / G) + NT - 1) / NT;  // horizontal-pass rounds per thread
+  static_assert(!ALIAS || ICP >= TC, "a window holds a plane of row sums");
+  __shared__ T sa[IR][ICP];
+  __shared__ T sb[IR][ICP];
+  __shared__ double hs[ALIAS ? 3 : 5][IR][TC];
+  __shared__ double red[NT / 64][PER_CHANNEL ? 4 : 2];
 
   const int tid = threadIdx.x;
   const int w3 = 3 * w;
@@ -102,7 +116,7 @@ __device__ __forceinline__ void tile_pass(const float* __restrict__ a, const flo
   const int own_c = blockIdx.x == gridDim.x - 1 ? ICP : TC;
 
   double sq = 0.0;
-  if (VEC) {  // w3 % 4 == 0 and 16-byte aligned bases: a chunk is inside the row or outside it
+  if constexpr (VEC) {  // w3 % 4 == 0 and 16-byte aligned bases: a chunk is inside the row or outside it
     for (int i = tid; i < IR * (ICP / 4); i += NT) {
       const int r = i / (ICP / 4), c = (i % (ICP / 4)) * 4;
       const int gr = r0 + r, gc = c0 + c;
@@ -125,7 +139,7 @@ __device__ __forceinline__ void tile_pass(const float* __restrict__ a, const flo
     for (int i = tid; i < IR * ICP; i += NT) {
       const int r = i / ICP, c = i % ICP;
       const int gr = r0 + r, gc = c0 + c;
-      float va = 0.f, vb = 0.f;
+      T va = 0, vb = 0;
       if (gr < h && gc < w3) {
         const long o = img + (long)gr * w3 + gc;
         va = a[o];
@@ -139,34 +153,91 @@ __device__ __forceinline__ void tile_pass(const float* __restrict__ a, const flo
   __syncthreads();
 
   // horizontal pass: thread = (row, base column cb); outputs cb + 3t, t < G, from inputs cb + 3m, m < GW
-  for (int i = tid; i < IR * (TC / G); i += NT) {
-    const int r = i / (TC / G), gi = i % (TC / G);
-    const int cb = (gi / 3) * (3 * G) + gi % 3;
-    double acc[5][G];
+  double (*hs3)[TC] = nullptr, (*hs4)[TC] = nullptr;  // ALIAS: the row sums of yy and xy
+  if constexpr (ALIAS) {
+    double keep[HI][2][G];  // yy and xy stay in registers until every thread has read the windows
 #pragma unroll
-    for (int k = 0; k < 5; ++k)
+    for (int it = 0; it < HI; ++it) {
+      const int i = tid + it * NT;
+      if (i < IR * (TC / G)) {
+        const int r = i / (TC / G), gi = i % (TC / G);
+        const int cb = (gi / 3) * (3 * G) + gi % 3;
+        double acc[5][G];  // (the else branch's sums: a shared helper changed the fp32 kernels' schedule)
 #pragma unroll
-      for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
+        for (int k = 0; k < 5; ++k)
 #pragma unroll
-    for (int m = 0; m < GW; ++m) {
-      const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
-      const double xx = x * x, yy = y * y, xy = x * y;
+          for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
 #pragma unroll
-      for (int t = 0; t < G; ++t) {
-        if (m - t >= 0 && m - t < NTAP) {
-          const double g = tp.g[m - t];
-          acc[0][t] = fma(g, x, acc[0][t]);
-          acc[1][t] = fma(g, y, acc[1][t]);
-          acc[2][t] = fma(g, xx, acc[2][t]);
-          acc[3][t] = fma(g, yy, acc[3][t]);
-          acc[4][t] = fma(g, xy, acc[4][t]);
+        for (int m = 0; m < GW; ++m) {
+          const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
+          const double xx = x * x, yy = y * y, xy = x * y;
+#pragma unroll
+          for (int t = 0; t < G; ++t) {
+            if (m - t >= 0 && m - t < NTAP) {
+              const double g = tp.g[m - t];
+              acc[0][t] = fma(g, x, acc[0][t]);
+              acc[1][t] = fma(g, y, acc[1][t]);
+              acc[2][t] = fma(g, xx, acc[2][t]);
+              acc[3][t] = fma(g, yy, acc[3][t]);
+              acc[4][t] = fma(g, xy, acc[4][t]);
+            }
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) hs[k][r][cb + 3 * t] = acc[k][t];
+          keep[it][0][t] = acc[3][t];
+          keep[it][1][t] = acc[4][t];
         }
       }
     }
+    __syncthreads();
+    hs3 = reinterpret_cast<double (*)[TC]>(&sa[0][0]);
+    hs4 = reinterpret_cast<double (*)[TC]>(&sb[0][0]);
 #pragma unroll
-    for (int k = 0; k < 5; ++k)
+    for (int it = 0; it < HI; ++it) {
+      const int i = tid + it * NT;
+      if (i < IR * (TC / G)) {
+        const int r = i / (TC / G), gi = i % (TC / G);
+        const int cb = (gi / 3) * (3 * G) + gi % 3;
 #pragma unroll
-      for (int t = 0; t < G; ++t) hs[k][r][cb + 3 * t] = acc[k][t];
+        for (int t = 0; t < G; ++t) {
+          hs3[r][cb + 3 * t] = keep[it][0][t];
+          hs4[r][cb + 3 * t] = keep[it][1][t];
+        }
+      }
+    }
+  } else {
+    for (int i = tid; i < IR * (TC / G); i += NT) {
+      const int r = i / (TC / G), gi = i % (TC / G);
+      const int cb = (gi / 3) * (3 * G) + gi % 3;
+      double acc[5][G];
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+#pragma unroll
+        for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
+#pragma unroll
+      for (int m = 0; m < GW; ++m) {
+        const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
+        const double xx = x * x, yy = y * y, xy = x * y;
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+          if (m - t >= 0 && m - t < NTAP) {
+            const double g = tp.g[m - t];
+            acc[0][t] = fma(g, x, acc[0][t]);
+            acc[1][t] = fma(g, y, acc[1][t]);
+            acc[2][t] = fma(g, xx, acc[2][t]);
+            acc[3][t] = fma(g, yy, acc[3][t]);
+            acc[4][t] = fma(g, xy, acc[4][t]);
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+#pragma unroll
+        for (int t = 0; t < G; ++t) hs[k][r][cb + 3 * t] = acc[k][t];
+    }
   }
   __syncthreads();
 
@@ -184,7 +255,11 @@ __device__ __forceinline__ void tile_pass(const float* __restrict__ a, const flo
     for (int m = 0; m < GW; ++m) {
       double v[5];
 #pragma unroll
-      for (int k = 0; k < 5; ++k) v[k] = hs[k][rb + m][c];
+      for (int k = 0; k < (ALIAS ? 3 : 5); ++k) v[k] = hs[k][rb + m][c];
+      if constexpr (ALIAS) {
+        v[3] = hs3[rb + m][c];
+        v[4] = hs4[rb + m][c];
+      }
 #pragma unroll
       for (int t = 0; t < G; ++t) {
         if (m - t >= 0 && m - t < NTAP) {
@@ -201,6 +276,20 @@ __device__ __forceinline__ void tile_pass(const float* __restrict__ a, const flo
         const double mxx = mx * mx, myy = my * my, mxy = mx * my;
         const double vx = acc[2][t] - mxx, vy = acc[3][t] - myy, cxy = acc[4][t] - mxy;
         const double a2 = 2.0 * cxy + c2, b2 = vx + vy + c2;
+        if constexpr (CS_ONLY) {
+          const double s = a2 / b2;
+          ss += s;
+          if constexpr (MODE == BASE_TERM_AND_PLANES) {
+            const double pc = 2.0 / b2;
+            const double pb = -2.0 * s / b2;
+            const long plane = (long)mh * mw3;
+            double* d = planes + (long)blockIdx.z * 3 * plane + (long)(r0 + rb + t) * mw3 + (c0 + c);
+            d[0] = -my * pc - mx * pb;
+            d[plane] = pb;
+            d[2 * plane] = pc;
+          }
+          continue;
+        }
         const double num = (2.0 * mxy + c1) * a2;
         const double den = (mxx + myy + c1) * b2;
         const double s = num / den;
@@ -220,12 +309,95 @@ __device__ __forceinline__ void tile_pass(const float* __restrict__ a, const flo
     }
   }
 
-  block_sum2(ss, sq, red);
-  if (tid == 0) {
-    const long nblk = (long)gridDim.x * gridDim.y;
-    double* d = part + ((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-    d[0] = ss;
-    d[1] = sq;
+  if constexpr (PER_CHANNEL) {
+    // the vertical pass gave this thread column tid % TC of a tile that starts at a red column
+    const int ch = (tid % TC) % 3;
+    double v[4] = {ch == 0 ? ss : 0.0, ch == 1 ? ss : 0.0, ch == 2 ? ss : 0.0, sq};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[k] = wave_sum_f64(v[k]);
+      if ((tid & 63) == 0) red[tid >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (tid < 4) {
+      double s = red[0][tid];
+      for (int i = 1; i < NT / 64; ++i) s += red[i][tid];
+      const long nblk = (long)gridDim.x * gridDim.y;
+      part[((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + tid] = s;
+    }
+  } else {
+    block_sum2(ss, sq, red);
+    if (tid == 0) {
+      const long nblk = (long)gridDim.x * gridDim.y;
+      double* d = part + ((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+      d[0] = ss;
+      d[1] = sq;
+    }
+  }
+}
+
+// The gradient filter of dssim.hip's pass 2 as a function: the workgroup of image tile
+// (blockIdx.y, blockIdx.x) leaves in f[k][t], for tid < (TR / G) * TC, the full (zero-padded)
+// correlation of plane k of image blockIdx.z of planes [n][3][mh][mw3] with the window at image
+// rows blockIdx.y * TR + (tid / TC) * G + t, float column blockIdx.x * TC + tid % TC.  One plane
+// at a time: stage the (TR+10) x (TC+30) window of the plane above and to the left of the tile
+// (zero outside the map), horizontal pass into fp64 row sums in LDS, vertical pass into registers.
+__device__ __forceinline__ void adjoint_pass(const double* __restrict__ planes, int mh, int mw3, Taps tp,
+                                             double (&f)[3][G]) {
+  static_assert((TR / G) * TC <= NT, "a thread's outputs stay in registers across the planes");
+  __shared__ double sp[IR][ICP];
+  __shared__ double hs[IR][TC];
+
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.y * TR, c0 = blockIdx.x * TC;
+  const long plane = (long)mh * mw3;
+  // the staged window's first map row / column: pixel (r, c) collects map rows r-10..r, columns c-30..c
+  const int q0 = r0 - 2 * R, p0 = c0 - 3 * 2 * R;
+  const int rb = (tid / TC) * G, c = tid % TC;  // this thread's outputs: rows rb..rb+3 of column c (tid < 192)
+
+#pragma unroll  // (f[k] stays in registers only with k a constant)
+  for (int k = 0; k < 3; ++k) {
+    const double* __restrict__ pk = planes + ((long)blockIdx.z * 3 + k) * plane;
+    for (int i = tid; i < IR * ICP; i += NT) {
+      const int r = i / ICP, cc = i % ICP;
+      const int qr = q0 + r, qc = p0 + cc;
+      double v = 0.0;
+      if (cc < IC && qr >= 0 && qr < mh && qc >= 0 && qc < mw3) v = pk[(long)qr * mw3 + qc];
+      sp[r][cc] = v;
+    }
+    __syncthreads();
+    // horizontal pass: staged column cb + 3m holds map column c0 + cb - 30 + 3m; output column
+    // cb + 3t takes it with tap g[10 - (m - t)]
+    for (int i = tid; i < IR * (TC / G); i += NT) {
+      const int r = i / (TC / G), gi = i % (TC / G);
+      const int cb = (gi / 3) * (3 * G) + gi % 3;
+      double acc[G];
+#pragma unroll
+      for (int t = 0; t < G; ++t) acc[t] = 0.0;
+#pragma unroll
+      for (int m = 0; m < GW; ++m) {
+        const double x = sp[r][cb + 3 * m];
+#pragma unroll
+        for (int t = 0; t < G; ++t)
+          if (m - t >= 0 && m - t < NTAP) acc[t] = fma(tp.g[NTAP - 1 - (m - t)], x, acc[t]);
+      }
+#pragma unroll
+      for (int t = 0; t < G; ++t) hs[r][cb + 3 * t] = acc[t];
+    }
+    __syncthreads();
+    // vertical pass into this thread's registers
+#pragma unroll
+    for (int t = 0; t < G; ++t) f[k][t] = 0.0;
+    if (tid < (TR / G) * TC) {
+#pragma unroll
+      for (int m = 0; m < GW; ++m) {
+        const double v = hs[rb + m][c];
+#pragma unroll
+        for (int t = 0; t < G; ++t)
+          if (m - t >= 0 && m - t < NTAP) f[k][t] = fma(tp.g[NTAP - 1 - (m - t)], v, f[k][t]);
+      }
+    }
+    __syncthreads();  // (sp and hs are written again for the next plane)
   }
 }
 

@@ -37,7 +37,7 @@ import torch
 from . import ops
 from . import optimizers as O
 from . import _lib as L
-from .losses import DSSIM
+from .losses import DSSIM, MSSSIM
 from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2DTranspose, Dropout,
                      InputLayer, MaxPooling2D)
 
@@ -705,17 +705,29 @@ class HeadStage(Stage):
         shape = (target.shape[0], e.h_valid, self.vin.w, 3)
         if tuple(target.shape) != shape:
             raise ValueError(f"DSSIM loss: target of shape {tuple(target.shape)}, prediction {shape}")
-        if e.h_valid < 11 or self.vin.w < 11:
+        if isinstance(e.dssim, MSSSIM):
+            need, m = e.dssim.min_side, len(e.dssim.power_factors)
+            if e.h_valid < need or self.vin.w < need:
+                raise ValueError(f"MSSSIM loss: a frame of {e.h_valid} x {self.vin.w} valid pixels is smaller than "
+                                 f"the {need} x {need} that {m} scales need (the coarsest holds SSIM's 11 x 11 "
+                                 f"window)")
+        elif e.h_valid < 11 or self.vin.w < 11:
             raise ValueError(f"DSSIM loss: a frame of {e.h_valid} x {self.vin.w} valid pixels is smaller than "
                              f"SSIM's 11 x 11 window")
 
+    def _dssim_out(self, y, target, dy=None, grad_frames=0.0):
+        """out [n, 3+] of the model's DSSIM or MSSSIM loss (column 2: L_i per image); writes dy where given."""
+        d = self.eng.dssim
+        if isinstance(d, MSSSIM):
+            return ops.msssim_loss_grad(d.base_id, d.alpha, d.power_factors, y, target, dy, grad_frames)
+        return ops.dssim_loss_grad(d.base_id, d.alpha, y, target, dy, grad_frames)
+
     def dssim_loss(self, n, target, loss_acc, yhat):
-        """The DSSIM loss and 'accuracy' of a prediction already in yhat, without a backward
-        kernel (evaluate_batch): loss_acc = [mean L_i, accuracy]."""
+        """The DSSIM / MSSSIM loss and 'accuracy' of a prediction already in yhat, without a
+        backward kernel (evaluate_batch): loss_acc = [mean L_i, accuracy]."""
         e = self.eng
         self._dssim_check(target)
-        d = e.dssim
-        out = ops.dssim_loss_grad(d.base_id, d.alpha, yhat, target)
+        out = self._dssim_out(yhat, target)
         count = ops.rgb_accuracy(yhat, target, torch.zeros(1, device=e.device, dtype=torch.int64))
         loss_acc[0] = out[:, 2].mean()
         loss_acc[1] = count[0] / float(yhat.numel() // 3)
@@ -733,13 +745,12 @@ class HeadStage(Stage):
         loss = e.loss_id  # 'mse' keeps its own entry points (the same kernels)
         dssim_out = None
         if loss == L.LOSS_GIVEN:
-            # DSSIM: the prediction, its loss and dL/dy, then the head with that gradient given
+            # DSSIM / MSSSIM: the prediction, its loss and dL/dy, then the head with that gradient given
             self._dssim_check(target)
-            d = e.dssim
             y = torch.empty(n, e.h_valid, self.vin.w, 3, device=e.device, dtype=torch.float32)
             ops.head_fwd(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), y, aff)
             dy = torch.empty_like(y)
-            dssim_out = ops.dssim_loss_grad(d.base_id, d.alpha, y, target, dy, grad_frames)
+            dssim_out = self._dssim_out(y, target, dy, grad_frames)
             if self._rank3():
                 g3 = torch.empty(P * 3, device=e.device, dtype=torch.float32)
                 ops.head_fwd_bwd_given(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), target, dy,
@@ -1054,17 +1065,18 @@ class Engine:
     # ---- loss / optimizer state ---------------------------------------------
     @property
     def loss_id(self):
-        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile); a DSSIM loss is
-        CNNITMO_LOSS_GIVEN: the head takes its gradient from cnnitmo_dssim_loss_grad."""
+        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile); a DSSIM or MSSSIM
+        loss is CNNITMO_LOSS_GIVEN: the head takes its gradient from cnnitmo_dssim_loss_grad /
+        cnnitmo_msssim_loss_grad."""
         if self.dssim is not None:
             return L.LOSS_GIVEN
         return L.LOSSES[getattr(self.model, "loss", None) or "mse"]
 
     @property
     def dssim(self):
-        """The model's losses.DSSIM, or None with a pointwise loss."""
+        """The model's losses.DSSIM or losses.MSSSIM, or None with a pointwise loss."""
         loss = getattr(self.model, "loss", None)
-        return loss if isinstance(loss, DSSIM) else None
+        return loss if isinstance(loss, (DSSIM, MSSSIM)) else None
 
     def ensure_slots(self, k):
         """At least k optimizer slot buffers (new ones zero, as Keras creates them)."""
@@ -1204,15 +1216,16 @@ class Engine:
         return loss_acc
 
     def evaluate_batch(self, x, target, image_metrics=()):
-        """Device tensor [loss, acc] of the batch.  image_metrics (names out of 'psnr', 'ssim'):
+        """Device tensor [loss, acc] of the batch.  image_metrics (names out of 'psnr', 'ssim', 'ms_ssim'):
         returns (loss_acc, per_image) with per_image a float64 [n, len(image_metrics)] device
-        tensor of the prediction against the target's valid rows (cnnitmo_image_metrics).  The
+        tensor of the prediction against the target's valid rows (cnnitmo_image_metrics; 'ms_ssim':
+        cnnitmo_msssim_loss_grad's loss-only form with TensorFlow's five weights).  The
         loss path is the same calls either way; the prediction is then written the way predict()
         writes it (the head in its producer's epilogue where fused, the head kernel otherwise)
         from the activations this forward left.  A DSSIM loss is a function of the prediction:
         it is written first, then cnnitmo_dssim_loss_grad's loss-only form and
         cnnitmo_rgb_accuracy give [loss, acc]; no backward kernel runs."""
-        cols = {"psnr": 1, "ssim": 2}
+        cols = {"psnr": 1, "ssim": 2, "ms_ssim": 3}
         if any(k not in cols for k in image_metrics):
             raise ValueError(f"image_metrics {image_metrics!r}: names out of {sorted(cols)}")
         head = self.stages[-1]
@@ -1255,5 +1268,12 @@ class Engine:
             head.infer(n, yhat)
             self._release()
         what = (ops.MSE_PSNR if "psnr" in image_metrics else 0) | (ops.SSIM if "ssim" in image_metrics else 0)
-        out = ops.image_metrics(what, yhat, target, 1.0)
+        if "ms_ssim" not in image_metrics:
+            out = ops.image_metrics(what, yhat, target, 1.0)
+            return loss_acc, out[:, [cols[k] for k in image_metrics]]
+        from . import metrics
+        out = torch.empty((yhat.shape[0], 4), dtype=torch.float64, device=self.device)
+        if what:
+            out[:, :3] = ops.image_metrics(what, yhat, target, 1.0)
+        out[:, 3] = metrics.ms_ssim(yhat, target)
         return loss_acc, out[:, [cols[k] for k in image_metrics]]

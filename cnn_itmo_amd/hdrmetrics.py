@@ -29,10 +29,13 @@ rank max(1, ceil(q h w)), so it is at or above it by less than a factor 1 + 1/64
   hdr_scales(pred, ref, align=, anchor=, ...)       -> (scale_pred, scale_ref) float64 [n]
   hdr_psnr_ssim(pred, ref, encoding='pq', ...)      -> (psnr [n], ssim [n]) float64
   hdr_psnr, hdr_ssim                                -> one of them
+  hdr_ms_ssim(pred, ref, encoding='pq', power_factors=None, ...)
+                                                    -> metrics.ms_ssim of the encoded planes [n]
 
 Inputs as in ``metrics.py``: numpy arrays or CUDA tensors, ``[h,w,3]`` or ``[n,h,w,3]``.  Every
 result is a CUDA tensor; the scales are formed from the device-side statistics with torch ops and
-nothing synchronises with the host.  SSIM needs images of at least 11 x 11 pixels.
+nothing synchronises with the host.  SSIM needs images of at least 11 x 11 pixels, MS-SSIM with
+its default five scales 161 x 161.
 """
 from __future__ import annotations
 
@@ -150,6 +153,20 @@ def hdr_psnr(pred, ref, encoding="pq", **kw):
     """Peak signal-to-noise ratio per image in dB of the encoded pair, float64 [n]."""
     from . import ops
     return _score(ops.MSE_PSNR, pred, ref, encoding, **kw)[0][:, 1]
+
+
+def hdr_ms_ssim(pred, ref, encoding="pq", power_factors=None, align="logmean", anchor="key", key=0.18,
+                white_nits=203.0, q=0.999, peak_nits=1000.0, lum=None):
+    """Multi-scale structural similarity per image of the encoded pair (metrics.ms_ssim with
+    max_val 1: the same align / anchor / encode as hdr_ssim), float64 [n]."""
+    from . import losses, metrics, ops
+    enc = _encoding_id(encoding)
+    p, r = _pair(pred, ref)
+    need = losses.min_side(len(losses.check_power_factors(power_factors)))
+    if p.shape[1] < need or p.shape[2] < need:  # (before any kernel runs, as for ssim)
+        raise ValueError(f"ms_ssim needs images of at least {need} x {need} pixels, got {p.shape[1]} x {p.shape[2]}")
+    sp, sr = _scales(p, r, align, anchor, key, white_nits, q, peak_nits, lum)
+    return metrics.ms_ssim(ops.hdr_encode(enc, p, sp), ops.hdr_encode(enc, r, sr), 1.0, power_factors)
 
 
 def hdr_ssim(pred, ref, encoding="pq", **kw):

@@ -123,7 +123,7 @@ def model_config(model):
 def training_config(model):
     from .model import _METRIC_CONFIG
     o = model.optimizer
-    # the compiled metrics in order ('accuracy', 'psnr', 'ssim'); load_model compiles with them
+    # the compiled metrics in order ('accuracy', 'psnr', 'ssim', 'ms_ssim'); load_model compiles with them
     metrics = [_METRIC_CONFIG[k] for k in getattr(model, "metrics_names", [])[1:]]
     return {"optimizer_config": {"class_name": o.class_name, "config": o.get_config()},
             "loss": losses.serialize(model.loss), "metrics": metrics,
@@ -302,7 +302,8 @@ def load_model_hdf5(path, compile=True):
         tc = json.loads(_str(f.attrs["training_config"]))
         oc = tc.get("optimizer_config", {})
         opt = optimizers.from_config(oc.get("class_name", "RMSprop"), oc.get("config", {}))
-        m.compile(opt, tc.get("loss", "mse"), tc.get("metrics") or ["accuracy"])
+        loss = tc.get("loss", "mse")
+        m.compile(opt, losses.get(loss) or loss, tc.get("metrics") or ["accuracy"])
         if "optimizer_weights" in f:
             # matched by order and shape, never by name: [iterations] + one tensor per trainable
             # weight and slot (+ Adam's shape-(1,) vhat placeholders, with or without)

@@ -30,7 +30,7 @@ from .layers import (LAYER_CLASSES, BatchNormalization, Conv2D, Conv2DTranspose,
 
 
 from . import losses, optimizers
-from .losses import DSSIM  # noqa: F401
+from .losses import DSSIM, MSSSIM  # noqa: F401
 from .optimizers import SGD, Adam, RMSprop  # noqa: F401  (keras.optimizers names, re-exported)
 
 # compile()'s loss names -> the canonical name (Model.loss, _lib.LOSSES)
@@ -41,16 +41,19 @@ _LOSS_NAMES = {"mse": "mse", "MSE": "mse", "mean_squared_error": "mse",
                "binary_crossentropy": "binary_crossentropy"}
 
 
-_METRIC_KEYS = {"accuracy": "acc", "acc": "acc", "categorical_accuracy": "acc", "psnr": "psnr", "ssim": "ssim"}
-_METRIC_CONFIG = {"acc": "accuracy", "psnr": "psnr", "ssim": "ssim"}  # the names training_config writes
+_METRIC_KEYS = {"accuracy": "acc", "acc": "acc", "categorical_accuracy": "acc", "psnr": "psnr", "ssim": "ssim",
+                "ms_ssim": "ms_ssim"}
+# the names training_config writes
+_METRIC_CONFIG = {"acc": "accuracy", "psnr": "psnr", "ssim": "ssim", "ms_ssim": "ms_ssim"}
 
 
 def _metric_key(m):
     """compile()'s metric -> its metrics_names / log key: 'accuracy' (Keras' categorical
-    accuracy of the 3 channels, shown as 'acc'), 'psnr', 'ssim' or metrics.psnr / metrics.ssim."""
+    accuracy of the 3 channels, shown as 'acc'), 'psnr', 'ssim', 'ms_ssim' or metrics.psnr /
+    metrics.ssim / metrics.ms_ssim."""
     if callable(m):
         from . import metrics as M
-        for k, f in (("psnr", M.psnr), ("ssim", M.ssim)):
+        for k, f in (("psnr", M.psnr), ("ssim", M.ssim), ("ms_ssim", M.ms_ssim)):
             if m is f:
                 return k
     elif isinstance(m, str) and m in _METRIC_KEYS:
@@ -99,7 +102,7 @@ class Model:
         self.layers = sorted(seen.values(), key=lambda l: l.seq)
         self._weights = {}  # internal-layout numpy weights (host copy, authoritative before engine)
         self.optimizer = None
-        self.loss = None         # once compiled: the canonical loss name, or a losses.DSSIM
+        self.loss = None         # once compiled: the canonical loss name, or a losses.DSSIM / MSSSIM
         self.engine = None
         self._dp = None          # dist.GradBucketer once distribute() was called
         self._dp_args = None
@@ -165,12 +168,17 @@ class Model:
     def compile(self, optimizer="rmsprop", loss="mse", metrics=None, dtype=None, **kwargs):
         """optimizer: 'rmsprop' / 'adam' / 'sgd' (any case) or an RMSprop / Adam / SGD instance;
         loss: 'mse', 'mae', 'logcosh', 'msle', 'binary_crossentropy' or a Keras alias of one
-        (_LOSS_NAMES); 'dssim' (1 - SSIM) or a losses.DSSIM(base, alpha), which ``Model.loss``
-        then holds.  Nothing changes when an argument is refused."""
+        (_LOSS_NAMES); 'dssim' (1 - SSIM), a losses.DSSIM(base, alpha) or a
+        losses.MSSSIM(base, alpha, power_factors), which ``Model.loss`` then holds.  The
+        multi-scale loss is taken as the object alone: its other forms ('ms_ssim', the saved
+        dict) are losses.get's, which load_model goes through.  Nothing changes when an
+        argument is refused."""
         optimizer = optimizers.get(optimizer)
         dssim = losses.get(loss)
+        if isinstance(dssim, MSSSIM) and dssim is not loss:
+            dssim = None  # ('ms_ssim' and the dict stay refused here, as tests/test_dssim_host.py holds)
         if dssim is None and (not isinstance(loss, str) or loss not in _LOSS_NAMES):
-            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES) + ['dssim']} or a DSSIM)")
+            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES) + ['dssim']}, a DSSIM or an MSSSIM)")
         if dtype not in (None, "float32", "bfloat16"):
             raise ValueError("dtype must be 'float32' or 'bfloat16'")
         names = []
@@ -186,7 +194,7 @@ class Model:
         self.optimizer = optimizer
         self.loss = dssim if dssim is not None else _LOSS_NAMES[loss]
         self.metrics_names = ["loss"] + names
-        # 'psnr' / 'ssim' in the order given: computed by evaluate() and for the validation logs
+        # 'psnr' / 'ssim' / 'ms_ssim' in the order given: computed by evaluate() and for the validation logs
         self.image_metrics = [k for k in names if k != "acc"]
         if dtype is not None:
             self.set_dtype(dtype)
@@ -339,7 +347,7 @@ class Model:
         return means, n
 
     def evaluate(self, x, y, batch_size=32, verbose=0):
-        """[loss, acc]; compiled with 'psnr' / 'ssim', the values of ``metrics_names`` in
+        """[loss, acc]; compiled with 'psnr' / 'ssim' / 'ms_ssim', the values of ``metrics_names`` in
         that order (image metrics are means of the per-image values, prediction against
         the target's valid rows; loss and acc are the same numbers either way)."""
         means, _ = self._evaluate_means(x, y, batch_size)
@@ -417,8 +425,8 @@ class Model:
         """keras Model.fit_generator (main.py:126-132): generator yields (x, y) batches.
 
         Epoch loss/acc are means over samples (per-step values weighted by batch size,
-        as Keras does).  Compiled with 'psnr' / 'ssim', the validation logs gain val_psnr /
-        val_ssim; the training-batch logs do not (the training head never stores its
+        as Keras does).  Compiled with 'psnr' / 'ssim' / 'ms_ssim', the validation logs gain val_psnr /
+        val_ssim / val_ms_ssim; the training-batch logs do not (the training head never stores its
         prediction).  A generator exposing ``last_global_batch`` (the rank-sharded
         ImageDataGenerator iterators, or a ``zip`` of two of them) gets global-batch-mean
         gradients under data parallelism (see train_on_batch).  ``distributed=True`` (or None with an initialised process group
@@ -665,7 +673,8 @@ def load_model(path, compile=True):
         m.set_named_weights({k[2:]: z[k] for k in z.files if k.startswith("w/")})
         if compile and "opt/config" in z.files:
             oc = json.loads(bytes(z["opt/config"]).decode())
-            m.compile(optimizers.from_config(oc["class_name"], oc["config"]), oc["loss"], oc["metrics"])
+            m.compile(optimizers.from_config(oc["class_name"], oc["config"]), losses.get(oc["loss"]) or oc["loss"],
+                      oc["metrics"])
         elif compile and "opt/hyper" in z.files:  # files from before the selectable optimizers
             lr, rho, eps = z["opt/hyper"].tolist()
             m.compile(RMSprop(lr=lr, rho=rho, epsilon=eps), "mse", ["accuracy"])

@@ -7,6 +7,7 @@ memory and the current HIP stream; every FLOP runs in libcnnitmo.so.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -509,6 +510,30 @@ def dssim_loss_grad(base, alpha, y, t, dy=None, grad_frames=0.0, out=None):
     ws = workspace(dssim_workspace_bytes(n, h, w, dy is not None), y.device)
     call("cnnitmo_dssim_loss_grad", base, float(alpha), ptr(y), ptr(t), n, h, w, float(grad_frames), ptr(out),
          ptr(dy), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out
+
+
+# ---------------------------------------------------------------- MS-SSIM metric and loss
+def msssim_workspace_bytes(n, h, w, scales, with_grad):
+    return query("cnnitmo_msssim_workspace_bytes", n, h, w, scales, int(bool(with_grad)))
+
+
+def msssim_loss_grad(base, alpha, power_factors, y, t, dy=None, grad_frames=0.0, max_val=1.0, out=None):
+    """y, t [n,h,w,3] contiguous fp32 device tensors -> out [n, 3 + 3 scales] fp64 = (ms_ssim, base
+    term, loss, the factors F[k][c]) per image; dy (optional, like y) = the gradient of the
+    batch-mean loss, normalised by grad_frames (0: n) frames (cnnitmo_msssim_loss_grad).  base: an
+    L.DSSIM_BASES id; power_factors: 1..5 host floats."""
+    n, h, w, c = y.shape
+    assert c == 3 and tuple(t.shape) == (n, h, w, 3), (tuple(y.shape), tuple(t.shape))
+    assert y.dtype == torch.float32 and t.dtype == torch.float32 and y.is_contiguous() and t.is_contiguous()
+    assert dy is None or (dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (n, h, w, 3))
+    m = len(power_factors)
+    pf = (ctypes.c_double * m)(*[float(v) for v in power_factors])
+    if out is None:
+        out = torch.empty((n, 3 + 3 * m), dtype=torch.float64, device=y.device)
+    ws = workspace(msssim_workspace_bytes(n, h, w, m, dy is not None), y.device)
+    call("cnnitmo_msssim_loss_grad", base, float(alpha), ctypes.addressof(pf), m, float(max_val), ptr(y), ptr(t), n, h,
+         w, float(grad_frames), ptr(out), ptr(dy), ws.data_ptr(), ws.numel(), stream_ptr())
     return out
 
 

@@ -110,15 +110,18 @@ def predict_frames(model, frames_u8, batch=8, cache=None, tile=None, return_floa
     return (outs, floats) if return_float else outs
 
 
-def score_png(pred_u8, ref_path):
+def score_png(pred_u8, ref_path, ms_ssim=False):
     """(psnr dB, ssim) of a written uint8 prediction against the PNG at ref_path, on the 0..255
-    values (max_val 255): what measuring the two files gives."""
+    values (max_val 255): what measuring the two files gives.  ``ms_ssim``: a third value,
+    metrics.ms_ssim of the same pair."""
     from . import metrics
     ref = np.array(read_png(ref_path))  # (a writable copy: PIL's buffer is read-only)
     if ref.shape != pred_u8.shape:
         raise ValueError(f"{ref_path}: reference is {ref.shape[1]}x{ref.shape[0]}, the prediction "
                          f"{pred_u8.shape[1]}x{pred_u8.shape[0]}")
     ps, ss = metrics.psnr_ssim(pred_u8, ref, max_val=255.0)
+    if ms_ssim:
+        return float(ps.item()), float(ss.item()), float(metrics.ms_ssim(pred_u8, ref, max_val=255.0).item())
     return float(ps.item()), float(ss.item())
 
 
@@ -145,11 +148,12 @@ def reference_log_average(ref_path):
 
 def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None, reference=None,
                 metrics_csv=None, hdr_dir=None, hdr_format="hdr", hdr_mode="script", hdr_key=0.18,
-                hdr_log_average=1.0, hdr_reference=None, hdr_metrics_csv=None):
+                hdr_log_average=1.0, hdr_reference=None, hdr_metrics_csv=None, ms_ssim=False):
     """``reference``: a directory of ground-truth PNGs; every written prediction is scored
     against the file of the same name there (PSNR / SSIM, logged per file and as the mean; a
     missing reference is reported and skipped, a size mismatch raises).  ``metrics_csv``:
-    also write ``name;psnr;ssim`` rows to that file.
+    also write ``name;psnr;ssim`` rows to that file.  ``ms_ssim``: also score the multi-scale
+    SSIM (images of at least 161 x 161 pixels), logged and as a further ``ms_ssim`` column.
     ``hdr_dir``: also write every prediction's HDR reconstruction there as ``name.hdr`` (Radiance
     RGBE) or ``name.pfm`` (``hdr_format``); ``hdr_mode`` 'script' applies inverse_Reinhard.m to
     the written 8-bit prediction, 'exact' the exact inverse of Reinhard.m (key ``hdr_key``,
@@ -217,18 +221,20 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
                 if not os.path.exists(ref):
                     log(f"{os.path.basename(f)}: no reference {ref}, not scored")
                     continue
-                ps, ss = score_png(p, ref)
-                log(f"{os.path.basename(f)}: psnr {ps:.4f} dB, ssim {ss:.6f}")
-                scores.append((os.path.basename(f), ps, ss))
+                ps, ss, *ms = score_png(p, ref, ms_ssim)
+                log(f"{os.path.basename(f)}: psnr {ps:.4f} dB, ssim {ss:.6f}"
+                    + "".join(f", ms_ssim {v:.6f}" for v in ms))
+                scores.append((os.path.basename(f), ps, ss, *ms))
     if reference is not None:
         if scores:
             log(f"mean of {len(scores)} scored files: psnr {np.mean([s[1] for s in scores]):.4f} dB, "
-                f"ssim {np.mean([s[2] for s in scores]):.6f}")
+                f"ssim {np.mean([s[2] for s in scores]):.6f}"
+                + (f", ms_ssim {np.mean([s[3] for s in scores]):.6f}" if ms_ssim else ""))
         if metrics_csv:
             with open(metrics_csv, "w", newline="") as fh:
-                fh.write("name;psnr;ssim\n")
-                for name, ps, ss in scores:
-                    fh.write(f"{name};{ps:.10g};{ss:.10g}\n")
+                fh.write("name;psnr;ssim" + (";ms_ssim" if ms_ssim else "") + "\n")
+                for name, *vals in scores:
+                    fh.write(name + "".join(f";{v:.10g}" for v in vals) + "\n")
     if hdr_reference is not None:
         EH.log_mean(log, hdr_scores)
         if hdr_metrics_csv:
@@ -253,6 +259,9 @@ def main(argv=None):
                     help="directory of ground-truth PNGs: score each written PNG against the same-named file "
                          "(PSNR and SSIM of the 8-bit images)")
     ap.add_argument("--metrics-csv", default=None, help="with --reference: write name;psnr;ssim rows to this file")
+    ap.add_argument("--ms-ssim", action="store_true",
+                    help="with --reference: also score the multi-scale SSIM (a further ms_ssim column in "
+                         "--metrics-csv)")
     ap.add_argument("--hdr", default=None, metavar="DIR",
                     help="also write each prediction's HDR reconstruction (inverse Reinhard) to DIR/name.hdr")
     ap.add_argument("--hdr-format", default="hdr", choices=["hdr", "pfm"],
@@ -272,6 +281,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.metrics_csv and not a.reference:
         ap.error("--metrics-csv needs --reference")
+    if a.ms_ssim and not a.reference:
+        ap.error("--ms-ssim needs --reference")
     if a.hdr_reference and not a.hdr:
         ap.error("--hdr-reference needs --hdr")
     if a.hdr_metrics_csv and not a.hdr_reference:
@@ -287,7 +298,7 @@ def main(argv=None):
     out = predict_dir(m, a.input, a.output, a.batch, tile=tile, reference=a.reference, metrics_csv=a.metrics_csv,
                       hdr_dir=a.hdr, hdr_format=a.hdr_format, hdr_mode=a.hdr_mode, hdr_key=a.hdr_key,
                       hdr_log_average=a.hdr_log_average, hdr_reference=a.hdr_reference,
-                      hdr_metrics_csv=a.hdr_metrics_csv)
+                      hdr_metrics_csv=a.hdr_metrics_csv, ms_ssim=a.ms_ssim)
     print(f"wrote {len(out)} predictions to {a.output}")
     if a.hdr:
         print(f"wrote {len(out)} .{a.hdr_format} reconstructions to {a.hdr}")

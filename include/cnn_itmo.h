@@ -605,6 +605,36 @@ long cnnitmo_dssim_workspace_bytes(int n, int h, int w, int with_grad);
 int cnnitmo_dssim_loss_grad(int base, double alpha, const float* y, const float* t, int n, int h, int w,
                             double grad_frames, double* out, float* dy, void* workspace, long workspace_bytes,
                             void* stream);
+/* ---------------------------------------------------------------------------
+ * Multi-scale SSIM (tf.image.ssim_multiscale) of a prediction y against a target t
+ * (fp32 [n][h][w][3], contiguous), per image i, as a metric and as a training loss:
+ *   level 0 = the image, level k+1 = the 2x2 mean of level k, an odd side first extended
+ *   by a copy of its last row / column (h' = ceil(h / 2));
+ *   F[k][c] = mean over the valid positions of level k, channel c, of cs (k < scales-1)
+ *             or of l cs (the last level): cnnitmo_image_metrics' window and moments,
+ *             C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2;
+ *   MS_c = prod_k max(F[k][c], 0)^power_factors[k],  ms_ssim = (MS_0 + MS_1 + MS_2) / 3;
+ *   L_i = alpha (1 - ms_ssim_i) + (1 - alpha) B_i, B_i and alpha as for the DSSIM loss.
+ * power_factors: host pointer to `scales` weights (1..5 of them, finite, >= 0), used as
+ * given.  The coarsest level must be at least 11 x 11: h, w >= 161 for five scales.
+ * out (device): double [n][3 + 3 scales] = {ms_ssim, B, L, F[0][0..2], F[1][0..2], ...}.
+ * dy (nullable, fp32 [n][h][w][3]) = d(sum_i L_i / F)/dy, F = grad_frames (<= 0: n); a
+ * channel with any factor <= 0 has MS_c = 0 and contributes exactly 0.  Every element is
+ * written exactly once.  A null dy gives the loss only: the same out bit for bit.
+ * fp64 after the loads, fixed-order reductions, no atomics: bitwise reproducible; the
+ * scalars of the gradient stay on the device (no host synchronisation).
+ * workspace: cnnitmo_msssim_workspace_bytes(n, h, w, scales, with_grad) bytes of device
+ * memory, 8-byte aligned, its contents irrelevant (0 for a bad shape; the query needs no
+ * GPU): the fp64 levels >= 1 of y and t (48 B per level pixel), the per-tile sums, and
+ * with_grad the coefficient planes of every level (72 B per map position) and the level
+ * gradients (24 B per level pixel): 16 B per pixel of the image for the loss alone, up to
+ * 120 B with the gradient.
+ * Stateless, never allocates; bad arguments are CNNITMO_EINVAL before any launch.
+ */
+long cnnitmo_msssim_workspace_bytes(int n, int h, int w, int scales, int with_grad);
+int cnnitmo_msssim_loss_grad(int base, double alpha, const double* power_factors, int scales, double max_val,
+                             const float* y, const float* t, int n, int h, int w, double grad_frames, double* out,
+                             float* dy, void* workspace, long workspace_bytes, void* stream);
 /* 'accuracy' of the head without a backward kernel: *count (device, zeroed by the caller) +=
  * the pixels out of npix whose argmax over RGB agrees between y and t [npix][3] fp32, with
  * the head kernels' tie rule (the first of equal channels). */
