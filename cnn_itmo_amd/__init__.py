@@ -8,7 +8,7 @@ from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2D
                      Input, InputLayer, MaxPooling2D, clear_session, concatenate)
 from .model import Model, load_model
 from .optimizers import SGD, Adam, RMSprop
-from .losses import DSSIM, MSSSIM
+from .losses import DSSIM, MSSSIM, HighlightWeighted
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import (CSVLogger, EarlyStopping, LambdaCallback, LearningRateScheduler, ModelCheckpoint,
                         ReduceLROnPlateau, TerminateOnNaN)
@@ -17,6 +17,6 @@ from .hdrgen import HDRPairGenerator, HDRPairIterator
 
 __all__ = ["HDRPairGenerator", "HDRPairIterator","Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
-           "Adam", "SGD", "DSSIM", "MSSSIM", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
+           "Adam", "SGD", "DSSIM", "MSSSIM", "HighlightWeighted", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
            "LambdaCallback", "ModelCheckpoint", "LearningRateScheduler", "ReduceLROnPlateau", "EarlyStopping",
            "TerminateOnNaN", "metrics", "hdrio", "hdrmetrics"]

@@ -129,6 +129,8 @@ SIGNATURES = {
     "cnnitmo_dssim_loss_grad": (i32, [i32, f64, vp, vp, i32, i32, i32, f64, vp, vp, vp, i64, vp]),
     "cnnitmo_msssim_workspace_bytes": (i64, [i32, i32, i32, i32, i32]),
     "cnnitmo_msssim_loss_grad": (i32, [i32, f64, vp, i32, f64, vp, vp, i32, i32, i32, f64, vp, vp, vp, i64, vp]),
+    "cnnitmo_highlight_workspace_bytes": (i64, [i32, i32, i32]),
+    "cnnitmo_highlight_loss_grad": (i32, [i32, f64, f64, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, i64, vp]),
     "cnnitmo_rgb_accuracy": (i32, [vp, vp, i64, vp, vp]),
     "cnnitmo_adam": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "cnnitmo_sgd": (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp]),

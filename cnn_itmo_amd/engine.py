@@ -37,7 +37,7 @@ import torch
 from . import ops
 from . import optimizers as O
 from . import _lib as L
-from .losses import DSSIM, MSSSIM
+from .losses import DSSIM, MSSSIM, HighlightWeighted
 from .layers import (Activation, BatchNormalization, Concatenate, Conv2D, Conv2DTranspose, Dropout,
                      InputLayer, MaxPooling2D)
 
@@ -703,6 +703,10 @@ class HeadStage(Stage):
     def _dssim_check(self, target):
         e = self.eng
         shape = (target.shape[0], e.h_valid, self.vin.w, 3)
+        if isinstance(e.dssim, HighlightWeighted):
+            if tuple(target.shape) != shape:
+                raise ValueError(f"HighlightWeighted loss: target of shape {tuple(target.shape)}, prediction {shape}")
+            return
         if tuple(target.shape) != shape:
             raise ValueError(f"DSSIM loss: target of shape {tuple(target.shape)}, prediction {shape}")
         if isinstance(e.dssim, MSSSIM):
@@ -716,15 +720,20 @@ class HeadStage(Stage):
                              f"SSIM's 11 x 11 window")
 
     def _dssim_out(self, y, target, dy=None, grad_frames=0.0):
-        """out [n, 3+] of the model's DSSIM or MSSSIM loss (column 2: L_i per image); writes dy where given."""
+        """out [n, 3+] of the model's DSSIM, MSSSIM or HighlightWeighted loss (column 2: L_i per
+        image); writes dy where given."""
         d = self.eng.dssim
+        if isinstance(d, HighlightWeighted):
+            # the mask source: the input frame's valid rows (the prediction's layout) or the target
+            s = self.eng.x_in if d.source == "input" else target
+            return ops.highlight_loss_grad(d.base_id, d.threshold, d.gain, s, y, target, dy, grad_frames)
         if isinstance(d, MSSSIM):
             return ops.msssim_loss_grad(d.base_id, d.alpha, d.power_factors, y, target, dy, grad_frames)
         return ops.dssim_loss_grad(d.base_id, d.alpha, y, target, dy, grad_frames)
 
     def dssim_loss(self, n, target, loss_acc, yhat):
-        """The DSSIM / MSSSIM loss and 'accuracy' of a prediction already in yhat, without a
-        backward kernel (evaluate_batch): loss_acc = [mean L_i, accuracy]."""
+        """The DSSIM / MSSSIM / HighlightWeighted loss and 'accuracy' of a prediction already in
+        yhat, without a backward kernel (evaluate_batch): loss_acc = [mean L_i, accuracy]."""
         e = self.eng
         self._dssim_check(target)
         out = self._dssim_out(yhat, target)
@@ -745,7 +754,8 @@ class HeadStage(Stage):
         loss = e.loss_id  # 'mse' keeps its own entry points (the same kernels)
         dssim_out = None
         if loss == L.LOSS_GIVEN:
-            # DSSIM / MSSSIM: the prediction, its loss and dL/dy, then the head with that gradient given
+            # DSSIM / MSSSIM / HighlightWeighted: the prediction, its loss and dL/dy, then the head with
+            # that gradient given
             self._dssim_check(target)
             y = torch.empty(n, e.h_valid, self.vin.w, 3, device=e.device, dtype=torch.float32)
             ops.head_fwd(e.dt, self.vin.view(n), e.h_valid, wt, e.p(self.name + "/bias"), y, aff)
@@ -1065,18 +1075,19 @@ class Engine:
     # ---- loss / optimizer state ---------------------------------------------
     @property
     def loss_id(self):
-        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile); a DSSIM or MSSSIM
-        loss is CNNITMO_LOSS_GIVEN: the head takes its gradient from cnnitmo_dssim_loss_grad /
-        cnnitmo_msssim_loss_grad."""
+        """CNNITMO_LOSS_* of the model's compiled loss ('mse' before compile); a DSSIM, MSSSIM or
+        HighlightWeighted loss is CNNITMO_LOSS_GIVEN: the head takes its gradient from
+        cnnitmo_dssim_loss_grad / cnnitmo_msssim_loss_grad / cnnitmo_highlight_loss_grad."""
         if self.dssim is not None:
             return L.LOSS_GIVEN
         return L.LOSSES[getattr(self.model, "loss", None) or "mse"]
 
     @property
     def dssim(self):
-        """The model's losses.DSSIM or losses.MSSSIM, or None with a pointwise loss."""
+        """The model's losses.DSSIM, losses.MSSSIM or losses.HighlightWeighted (the losses whose
+        gradient the head is given), or None with a pointwise loss."""
         loss = getattr(self.model, "loss", None)
-        return loss if isinstance(loss, (DSSIM, MSSSIM)) else None
+        return loss if isinstance(loss, (DSSIM, MSSSIM, HighlightWeighted)) else None
 
     def ensure_slots(self, k):
         """At least k optimizer slot buffers (new ones zero, as Keras creates them)."""

@@ -11,6 +11,13 @@ the head takes the gradient through cnnitmo_head_fwd_bwd_given (engine.HeadStage
 MSSSIM: the same mix with the multi-scale SSIM of ``metrics.ms_ssim`` (tf.image.ssim_multiscale)
 in SSIM's place, the form Zhao et al. found to train better than single-scale SSIM: it also sees
 errors wider than the 11-pixel window.  Loss and gradient are cnnitmo_msssim_loss_grad.
+
+HighlightWeighted: the pointwise L2 / L1 loss with every pixel weighted by 1 + gain * a, a the soft
+saturation mask of Eilertsen et al. 2017 ("HDR image reconstruction from a single exposure using
+deep CNNs"), a = clip((max_c s - threshold) / (1 - threshold), 0, 1), taken from the network's
+input frame or from the target: the clipped pixels are the ones an inverse tone-mapping network
+has to invent, and a few percent of a frame.  Loss and gradient are cnnitmo_highlight_loss_grad;
+``highlight_weighted`` is the functional form, for reporting the error inside the highlights.
 """
 from __future__ import annotations
 
@@ -90,6 +97,71 @@ class MSSSIM:
         return f"MSSSIM(base={self.base!r}, alpha={self.alpha!r}, power_factors={self.power_factors!r})"
 
 
+class HighlightWeighted:
+    """compile(loss=HighlightWeighted(base='mse' | 'mae', threshold=0.95, gain=1.0, source='input' |
+    'target')): per image the mean over pixels and channels of (1 + gain * a) * l, l = (y-t)^2 or
+    |y-t|, a = clip((max_c s - threshold) / (1 - threshold), 0, 1).  source 'input': s is the
+    network's input frame (where the camera clipped); 'target': s is the target (its bright
+    regions).  The sum is divided by the element count, not by the sum of the weights: gain 0 is
+    the base loss and unsaturated pixels keep the gradient they have under it.  threshold 0.95 is
+    HDRCNN's tau; gain 1.0 is a starting point, not a tuned value."""
+
+    class_name = "HighlightWeighted"
+
+    def __init__(self, base="mse", threshold=0.95, gain=1.0, source="input"):
+        if base not in ("mse", "mae"):
+            raise ValueError(f"HighlightWeighted base {base!r} (one of 'mse', 'mae')")
+        if source not in ("input", "target"):
+            raise ValueError(f"HighlightWeighted source {source!r} (one of 'input', 'target')")
+        try:
+            threshold, gain = float(threshold), float(gain)
+        except (TypeError, ValueError):
+            raise ValueError(f"HighlightWeighted threshold {threshold!r}, gain {gain!r}: two numbers") from None
+        if not 0.0 <= threshold < 1.0:  # (NaN fails both)
+            raise ValueError(f"HighlightWeighted threshold {threshold!r} outside [0, 1)")
+        if not 0.0 <= gain < float("inf"):
+            raise ValueError(f"HighlightWeighted gain {gain!r} negative or not finite")
+        self.base, self.threshold, self.gain, self.source = base, threshold, gain, source
+
+    @property
+    def base_id(self):
+        return L.DSSIM_BASES[self.base]
+
+    def get_config(self):
+        return {"base": self.base, "threshold": self.threshold, "gain": self.gain, "source": self.source}
+
+    def _key(self):
+        return self.base, self.threshold, self.gain, self.source
+
+    def __eq__(self, other):
+        return isinstance(other, HighlightWeighted) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash((self.class_name,) + self._key())
+
+    def __repr__(self):
+        return (f"HighlightWeighted(base={self.base!r}, threshold={self.threshold!r}, gain={self.gain!r}, "
+                f"source={self.source!r})")
+
+
+def highlight_weighted(x, y, t, base="mse", threshold=0.95, gain=1.0, source="input"):
+    """The highlight-weighted loss of predictions y against targets t for the input frames x, per
+    image: a float64 [n, 4] CUDA tensor {A, B, L, H} = the mean mask (the saturated share), the
+    unweighted base term, the loss HighlightWeighted(base, threshold, gain, source) trains for and
+    the base error inside the highlights (sum a l / (3 sum a), 0 without a masked pixel).  x, y, t:
+    numpy arrays or CUDA tensors, [h,w,3] or [n,h,w,3]; with source 'target' x is not read (None
+    will do).  Nothing synchronises with the host."""
+    import torch
+    from . import ops
+    from .tonemap import _dev
+    hw = HighlightWeighted(base, threshold, gain, source)
+    y, t = _dev(y, torch.float32), _dev(t, torch.float32)
+    s = t if source == "target" else _dev(x, torch.float32)
+    if not y.shape == t.shape == s.shape:
+        raise ValueError(f"image batches differ in shape: {tuple(s.shape)}, {tuple(y.shape)}, {tuple(t.shape)}")
+    return ops.highlight_loss_grad(hw.base_id, hw.threshold, hw.gain, s, y, t)
+
+
 MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)  # tf.image.ssim_multiscale's power_factors
 
 
@@ -113,9 +185,9 @@ def check_power_factors(power_factors):
 
 
 def get(loss):
-    """The forms of a structural loss -> its object: a DSSIM or an MSSSIM, 'dssim', 'ms_ssim' /
-    'msssim' (1 - MS-SSIM), or serialize()'s dict; else None."""
-    if isinstance(loss, (DSSIM, MSSSIM)):
+    """The forms of a loss of this module -> its object: a DSSIM, an MSSSIM or a HighlightWeighted,
+    'dssim', 'ms_ssim' / 'msssim' (1 - MS-SSIM), or serialize()'s dict; else None."""
+    if isinstance(loss, (DSSIM, MSSSIM, HighlightWeighted)):
         return loss
     if isinstance(loss, str) and loss in ("dssim", "DSSIM"):
         return DSSIM()
@@ -125,13 +197,15 @@ def get(loss):
         return DSSIM(**loss.get("config", {}))
     if isinstance(loss, dict) and loss.get("class_name") == MSSSIM.class_name:
         return MSSSIM(**loss.get("config", {}))
+    if isinstance(loss, dict) and loss.get("class_name") == HighlightWeighted.class_name:
+        return HighlightWeighted(**loss.get("config", {}))
     return None
 
 
 def serialize(loss):
     """Model.loss as the saved training config holds it: the canonical name of a pointwise
-    loss, {'class_name': 'DSSIM' | 'MSSSIM', 'config': {...}} for a DSSIM or an MSSSIM (json keeps
-    alpha and the weights exactly)."""
-    if isinstance(loss, (DSSIM, MSSSIM)):
+    loss, {'class_name': 'DSSIM' | 'MSSSIM' | 'HighlightWeighted', 'config': {...}} for an object of
+    this module (json keeps alpha, the weights, threshold and gain exactly)."""
+    if isinstance(loss, (DSSIM, MSSSIM, HighlightWeighted)):
         return {"class_name": loss.class_name, "config": loss.get_config()}
     return loss

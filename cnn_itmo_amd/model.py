@@ -30,7 +30,7 @@ from .layers import (LAYER_CLASSES, BatchNormalization, Conv2D, Conv2DTranspose,
 
 
 from . import losses, optimizers
-from .losses import DSSIM, MSSSIM  # noqa: F401
+from .losses import DSSIM, MSSSIM, HighlightWeighted  # noqa: F401
 from .optimizers import SGD, Adam, RMSprop  # noqa: F401  (keras.optimizers names, re-exported)
 
 # compile()'s loss names -> the canonical name (Model.loss, _lib.LOSSES)
@@ -102,7 +102,8 @@ class Model:
         self.layers = sorted(seen.values(), key=lambda l: l.seq)
         self._weights = {}  # internal-layout numpy weights (host copy, authoritative before engine)
         self.optimizer = None
-        self.loss = None         # once compiled: the canonical loss name, or a losses.DSSIM / MSSSIM
+        # once compiled: the canonical loss name, or a losses.DSSIM / MSSSIM / HighlightWeighted
+        self.loss = None
         self.engine = None
         self._dp = None          # dist.GradBucketer once distribute() was called
         self._dp_args = None
@@ -168,17 +169,19 @@ class Model:
     def compile(self, optimizer="rmsprop", loss="mse", metrics=None, dtype=None, **kwargs):
         """optimizer: 'rmsprop' / 'adam' / 'sgd' (any case) or an RMSprop / Adam / SGD instance;
         loss: 'mse', 'mae', 'logcosh', 'msle', 'binary_crossentropy' or a Keras alias of one
-        (_LOSS_NAMES); 'dssim' (1 - SSIM), a losses.DSSIM(base, alpha) or a
-        losses.MSSSIM(base, alpha, power_factors), which ``Model.loss`` then holds.  The
-        multi-scale loss is taken as the object alone: its other forms ('ms_ssim', the saved
-        dict) are losses.get's, which load_model goes through.  Nothing changes when an
-        argument is refused."""
+        (_LOSS_NAMES); 'dssim' (1 - SSIM), a losses.DSSIM(base, alpha), a
+        losses.MSSSIM(base, alpha, power_factors) or a losses.HighlightWeighted(base, threshold,
+        gain, source), which ``Model.loss`` then holds.  The multi-scale loss is taken as the
+        object alone: its other forms ('ms_ssim', the saved dict) are losses.get's, which
+        load_model goes through; a HighlightWeighted also as losses.serialize's dict.  Nothing
+        changes when an argument is refused."""
         optimizer = optimizers.get(optimizer)
         dssim = losses.get(loss)
         if isinstance(dssim, MSSSIM) and dssim is not loss:
             dssim = None  # ('ms_ssim' and the dict stay refused here, as tests/test_dssim_host.py holds)
         if dssim is None and (not isinstance(loss, str) or loss not in _LOSS_NAMES):
-            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES) + ['dssim']}, a DSSIM or an MSSSIM)")
+            raise NotImplementedError(f"loss {loss!r} (one of {sorted(_LOSS_NAMES) + ['dssim']}, a DSSIM or an MSSSIM"
+                                      f", or a HighlightWeighted)")
         if dtype not in (None, "float32", "bfloat16"):
             raise ValueError("dtype must be 'float32' or 'bfloat16'")
         names = []

@@ -537,6 +537,29 @@ def msssim_loss_grad(base, alpha, power_factors, y, t, dy=None, grad_frames=0.0,
     return out
 
 
+# ---------------------------------------------------------------- highlight-weighted loss
+def highlight_workspace_bytes(n, h, w):
+    return query("cnnitmo_highlight_workspace_bytes", n, h, w)
+
+
+def highlight_loss_grad(base, tau, gain, s, y, t, dy=None, grad_frames=0.0, out=None):
+    """s (the mask source; may be t), y, t [n,h,w,3] contiguous fp32 device tensors -> out [n,4] fp64 =
+    (mean mask, base term, loss, base error inside the highlights) per image; dy (optional, like y) =
+    the gradient of the batch-mean loss, normalised by grad_frames (0: n) frames
+    (cnnitmo_highlight_loss_grad).  base: the L.DSSIM_BASES id of 'mae' or 'mse'."""
+    n, h, w, c = y.shape
+    assert c == 3 and tuple(t.shape) == (n, h, w, 3) and tuple(s.shape) == (n, h, w, 3), \
+        (tuple(s.shape), tuple(y.shape), tuple(t.shape))
+    assert all(v.dtype == torch.float32 and v.is_contiguous() for v in (s, y, t))
+    assert dy is None or (dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (n, h, w, 3))
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.float64, device=y.device)
+    ws = workspace(highlight_workspace_bytes(n, h, w), y.device)
+    call("cnnitmo_highlight_loss_grad", base, float(tau), float(gain), ptr(s), ptr(y), ptr(t), n, h, w,
+         float(grad_frames), ptr(out), ptr(dy), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out
+
+
 def rgb_accuracy(y, t, count):
     """count (int64 [1], device) += the pixels of y, t [..., 3] whose argmax over RGB agrees."""
     assert y.dtype == torch.float32 and t.dtype == torch.float32 and y.is_contiguous() and t.is_contiguous()

@@ -635,6 +635,34 @@ long cnnitmo_msssim_workspace_bytes(int n, int h, int w, int scales, int with_gr
 int cnnitmo_msssim_loss_grad(int base, double alpha, const double* power_factors, int scales, double max_val,
                              const float* y, const float* t, int n, int h, int w, double grad_frames, double* out,
                              float* dy, void* workspace, long workspace_bytes, void* stream);
+/* ---------------------------------------------------------------------------
+ * Highlight-weighted training loss of a prediction y against a target t, the mask taken
+ * from a source image s (all fp32 [n][h][w][3], contiguous; s may be t).  Per pixel p
+ *   m = max over the channels of s[p],  a = fmin(fmax((m - tau) / (1 - tau), 0), 1)
+ *       (the soft saturation mask of Eilertsen et al. 2017; a NaN gives 0, m == tau exactly 0),
+ *   wgt = 1 + gain a,  l = (y-t)^2 (CNNITMO_BASE_MSE) or |y-t| (CNNITMO_BASE_MAE),
+ * and per image i, N = h*w*3:
+ *   A_i = sum_p a / (h w)          the mean mask
+ *   B_i = sum l / N                the unweighted base term
+ *   L_i = sum wgt l / N            the loss: not divided by sum wgt, so gain 0 is the base
+ *                                  loss and unmasked pixels keep the base loss's gradient
+ *   H_i = sum a l / (3 sum_p a)    the base error inside the highlights, 0 if sum_p a == 0
+ * tau in [0, 1), gain >= 0 and finite, base MAE or MSE (CNNITMO_BASE_NONE is refused).
+ * out (device): double [n][4] = {A, B, L, H}.  dy (nullable, fp32 [n][h][w][3]) =
+ * (float)((wgt l') / (F N)), l' = 2 (y-t) or sign(y-t) with sign(0) = 0, F = grad_frames
+ * (<= 0: n); every element is written exactly once.  A null dy gives the same out bit for
+ * bit.  fp64 after the loads, no FMA contraction, fixed-order reductions, no atomics:
+ * bitwise reproducible, and the same bits whether the images are 16-byte aligned (16-byte
+ * loads and stores, four pixels a thread) or not (one float at a time).
+ * workspace: cnnitmo_highlight_workspace_bytes(n, h, w) bytes of device memory (32 per
+ * 1024 pixels of an image), 8-byte aligned, its contents irrelevant (<= 0 for a bad
+ * shape; the query needs no GPU).
+ * Stateless, never allocates; bad arguments are CNNITMO_EINVAL before any launch.
+ */
+long cnnitmo_highlight_workspace_bytes(int n, int h, int w);
+int cnnitmo_highlight_loss_grad(int base, double tau, double gain, const float* s, const float* y, const float* t,
+                                int n, int h, int w, double grad_frames, double* out, float* dy, void* workspace,
+                                long workspace_bytes, void* stream);
 /* 'accuracy' of the head without a backward kernel: *count (device, zeroed by the caller) +=
  * the pixels out of npix whose argmax over RGB agrees between y and t [npix][3] fp32, with
  * the head kernels' tie rule (the first of equal channels). */
