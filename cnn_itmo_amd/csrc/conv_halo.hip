@@ -1023,6 +1023,7 @@ bool halo_plan(const FwdArgs& a, HaloPlan& pl, bool f32 = false) {
   // (fp32: 82.9 -> 94.8 frames/s at 1080p b8 inference, the kernel at 0.87 of fp32 peak
   // against the implicit GEMM's 0.75, profiles/r03zl_*)
   if (!en) return false;
+  if (a.cin <= 0 || a.N <= 0 || a.M <= 0) return false;  // nothing to launch (and no N / bn = 0 column blocks)
   if (f32) {
     if (a.cin % 16 || a.a_ld % 4 || a.a_off % 4 || a.out_ld % 4 || a.out_off % 4) return false;
     if (a.a2) return false;

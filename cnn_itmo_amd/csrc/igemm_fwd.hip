@@ -283,8 +283,19 @@ int launch_fwd(FwdArgs a, hipStream_t s, const char* what) {
   return cnnitmo_check_launch(what);
 }
 
+// The sizes launch_fwd / launch_fwd2 take from dense views (their CNN_REQUIREs): the queries give
+// a shape that fails them no rows and no kernel name.
+bool igemm_sizes_ok(int dtype, const FwdArgs& a) {
+  if (dtype != CNNITMO_BF16 && dtype != CNNITMO_F32) return false;
+  const int ve = dtype == CNNITMO_BF16 ? 8 : 4;  // Vec16<T>::N
+  if (a.M <= 0 || a.N <= 0 || a.cin <= 0 || a.N % 32 || a.a_ld % ve || a.out_ld % ve) return false;
+  if (fwd2_handles(a.N)) return a.cin % ve == 0 && (!a.scatter || a.cout % ve == 0);
+  return a.cin % (4 * ve) == 0;
+}
+
 int dispatch(int dtype, const FwdArgs& a, void* stream, const char* what) {
   hipStream_t s = (hipStream_t)stream;
+  CNN_REQUIRE(a.M > 0 && a.N > 0 && a.cin > 0, "%s: empty (%ld pixels, %d -> %d channels)", what, a.M, a.cin, a.N);
   if (dtype == CNNITMO_BF16 && halo_handles(a)) return launch_halo(a, s, what);
   if (dtype == CNNITMO_F32 && halo_handles(a, true)) return launch_halo(a, s, what, true);
   if (fwd2_handles(a.N)) {
@@ -327,6 +338,7 @@ extern "C" long cnnitmo_conv3x3_stat_rows(int dtype, int n, int h, int w, int ci
   a.cin = cin; a.N = cout; a.a_ld = cin; a.out_ld = cout; a.M = (long)n * h * w;
   if (dtype == CNNITMO_BF16 && halo_handles(a)) return halo_stat_rows(a);
   if (dtype == CNNITMO_F32 && halo_handles(a, true)) return halo_stat_rows(a, true);
+  if (!igemm_sizes_ok(dtype, a)) return 0;
   return cnnitmo_fwd_stat_rows(dtype, a.M, cout);
 }
 
@@ -353,11 +365,13 @@ extern "C" long cnnitmo_tconv2x2_stat_rows(int dtype, int n, int h, int w, int c
   a.cin = cin; a.N = 4 * cout; a.a_ld = cin; a.out_ld = cout; a.M = (long)n * h * w;
   a.scatter = 1; a.cout = cout;
   if (dtype == CNNITMO_BF16 && halo_handles(a)) return halo_stat_rows(a);
+  if (!igemm_sizes_ok(dtype, a)) return 0;
   return cnnitmo_fwd_stat_rows(dtype, a.M, 4 * cout);
 }
 
 extern "C" int cnnitmo_fwd_stat_rows(int dtype, long m, int ncols) {
   (void)dtype;
+  if (m <= 0 || ncols <= 0 || ncols % 32) return 0;  // (launch_fwd / launch_fwd2 refuse these)
   if (fwd2_handles(ncols)) return fwd2_stat_rows(m);
   Cfg c = pick_cfg(ncols);
   return (int)((m + c.bm - 1) / c.bm);
@@ -511,6 +525,7 @@ extern "C" const char* cnnitmo_conv3x3_kernel_name(int dtype, int n, int h, int 
   static thread_local char buf[96];
   if (dtype == CNNITMO_BF16 && halo_handles(a)) return halo_name(a);
   if (dtype == CNNITMO_F32 && halo_handles(a, true)) return halo_name(a, true);  // (no BN sums: inference)
+  if (!igemm_sizes_ok(dtype, a)) return "";
   const char* t = dtype == CNNITMO_BF16 ? "bf16" : "f32";
   if (fwd2_handles(a.N)) {
     const int bn = a.N % 128 == 0 ? 128 : a.N % 64 == 0 ? 64 : a.N % 96 == 0 ? 96 : 32;
@@ -549,6 +564,7 @@ extern "C" const char* cnnitmo_tconv2x2_kernel_name(int dtype, int n, int h, int
   }
   a.M = (long)n * h * w;
   if (dtype == CNNITMO_BF16 && halo_handles(a)) return halo_name(a);
+  if (!igemm_sizes_ok(dtype, a)) return "";
   static thread_local char buf[96];
   const char* t = dtype == CNNITMO_BF16 ? "bf16" : "f32";
   if (fwd2_handles(a.N)) {

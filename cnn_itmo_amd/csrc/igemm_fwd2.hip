@@ -742,6 +742,7 @@ static int cu_count();
 // a kernel with a different stat-row count.
 bool tfwd2p_handles(const FwdArgs& a, bool bf16) {
   const int gx = std::max(cu_count() / 8, 1);
+  if (a.N <= 0 || a.M <= 0 || a.cin <= 0) return false;  // nothing to launch (and no gx % 0 below)
   return bf16 && a.scatter && a.ntaps == 1 && a.N % 256 == 0 && a.cin % 64 == 0 && a.cout % 8 == 0 &&
          !a.border && !(a.flags & ~(CNNITMO_RELU | CNNITMO_STATS | CNNITMO_BIAS_PER_COL | CNNITMO_AFFINE)) &&
          a.M < (1L << 31) && gx % (a.N / 256) == 0;

@@ -373,6 +373,12 @@ struct Plan {
   long pps;
 };
 
+// the sizes run_wgrad takes (its CNN_REQUIREs): anything else gets no workspace and no kernel
+// name from the queries -- make_plan would divide by zero tiles
+bool sizes_ok(long P, int M, int N, int ntaps) {
+  return P > 0 && M > 0 && N > 0 && M % 32 == 0 && N % 32 == 0 && ntaps > 0;
+}
+
 template <typename T>
 Plan make_plan(long P, int M, int N, int ntaps) {
   Plan pl;
@@ -426,8 +432,8 @@ int try_wgrad2(const WgradArgs& a, int tapdep, void* ws, size_t ws_bytes, hipStr
 template <typename T>
 int run_wgrad(WgradArgs a, float* out_final, int rows, int cols_in, int cols_out, void* ws,
               size_t ws_bytes, hipStream_t s, const char* what, const WFold& fold, int tapdep = 0) {
-  CNN_REQUIRE(a.M % 32 == 0 && a.N % 32 == 0, "%s: channel counts %d/%d must be multiples of 32",
-              what, a.M, a.N);
+  CNN_REQUIRE(a.M > 0 && a.N > 0 && a.M % 32 == 0 && a.N % 32 == 0,
+              "%s: channel counts %d/%d must be positive multiples of 32", what, a.M, a.N);
   CNN_REQUIRE(a.a_ld % Vec16<T>::N == 0 && a.b_ld % Vec16<T>::N == 0 && a.b_off % Vec16<T>::N == 0,
               "%s: views must be 16-byte aligned", what);
   a.P = (long)a.nimg * a.hg * a.wg;
@@ -461,6 +467,7 @@ int run_wgrad(WgradArgs a, float* out_final, int rows, int cols_in, int cols_out
 
 template <typename T>
 size_t ws_bytes_for(long P, int M, int N, int ntaps) {
+  if (!sizes_ok(P, M, N, ntaps)) return 0;
   Plan pl = make_plan<T>(P, M, N, ntaps);
   size_t b = (size_t)pl.splits * M * N * ntaps * 4;
   if (std::is_same<T, bf16>::value) b = std::max(b, wgrad2_ws_bytes(P, M, N, ntaps));
@@ -639,6 +646,10 @@ extern "C" const char* cnnitmo_wgrad_cat_kernel_name(int n, int h, int w, int c1
 
 extern "C" const char* cnnitmo_wgrad_kernel_name(int dtype, int ntaps, int n, int h, int w, int cin,
                                                  int cout) {
+  // sizes the launch refuses (run_wgrad's requirements) have no kernel
+  if ((dtype != CNNITMO_BF16 && dtype != CNNITMO_F32) || (ntaps != 1 && ntaps != 4 && ntaps != 9) ||
+      !sizes_ok((long)n * h * w, cout, cin, ntaps))
+    return "";
   if (dtype == CNNITMO_BF16 && ntaps == 9) {
     const char* hn = wgrad_halo_name(n, h, w, cin, cout);
     if (hn[0]) return hn;

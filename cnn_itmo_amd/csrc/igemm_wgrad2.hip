@@ -250,6 +250,12 @@ static void w2_tiles(int M, int N, int ntaps, int& bm, int& bn, int& tpb) {
   if (bm * bn >= 128 * 64 && tpb > 3) tpb = ntaps == 4 ? 2 : 3;
 }
 
+// the sizes w2_plan can tile: positive multiples of 32 channels, at least one pixel and tap
+// (anything else: no workspace, no label, launch_wgrad2 < 0 -- never a division by zero tiles)
+static bool w2_sizes_ok(long P, int M, int N, int ntaps) {
+  return P > 0 && M > 0 && N > 0 && M % 32 == 0 && N % 32 == 0 && ntaps > 0;
+}
+
 static W2Plan w2_plan(long P, int M, int N, int ntaps) {
   W2Plan pl;
   w2_tiles(M, N, ntaps, pl.bm, pl.bn, pl.tpb);
@@ -269,6 +275,7 @@ static W2Plan w2_plan(long P, int M, int N, int ntaps) {
 }
 
 size_t wgrad2_ws_bytes(long P, int M, int N, int ntaps) {
+  if (!w2_sizes_ok(P, M, N, ntaps)) return 0;
   const W2Plan pl = w2_plan(P, M, N, ntaps);
   return (size_t)pl.splits * M * N * ntaps * 4;
 }
@@ -305,6 +312,7 @@ static bool w2_dispatch(const Wgrad2Args& a, const W2Plan& pl, hipStream_t s, un
 // unsupported or the workspace is too small (caller falls back to v1).
 int launch_wgrad2(Wgrad2Args a, void* ws, size_t ws_bytes, hipStream_t s) {
   a.P = (long)a.nimg * a.hg * a.wg;
+  if (!w2_sizes_ok(a.P, a.M, a.N, a.ntaps)) return -1;
   const W2Plan pl = w2_plan(a.P, a.M, a.N, a.ntaps);
   const long slab = (long)a.M * a.N * a.ntaps;
   if (!ws || ws_bytes < (size_t)pl.splits * slab * 4) return -1;
@@ -320,6 +328,7 @@ int launch_wgrad2(Wgrad2Args a, void* ws, size_t ws_bytes, hipStream_t s) {
 }
 
 W2Label wgrad2_label(long P, int M, int N, int ntaps) {
+  if (!w2_sizes_ok(P, M, N, ntaps)) return W2Label{false, 0, 0, 0};
   const W2Plan pl = w2_plan(P, M, N, ntaps);
   W2Label l{false, pl.bm, pl.bn, pl.tpb};
   Wgrad2Args a;

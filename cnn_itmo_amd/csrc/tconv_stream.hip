@@ -441,7 +441,7 @@ struct TSPlan {
 };
 
 bool ts_plan(int mode, int h, int w, int cin, int cout, bool epi, TSPlan& pl) {
-  if (w < 1 || h < 1) return false;
+  if (w < 1 || h < 1 || cin < 1 || cout < 1) return false;  // (K = 0 would divide by zero below)
   const int K = mode == 0 ? cin : 4 * cout, N = mode == 0 ? 4 * cout : cin;
   if (K % 128 || cout % 32 || N % 64) return false;
   int bn = 64 * 1024 / (K * 2);  // the resident weight block: K x BN bf16 <= 64 KB

@@ -361,7 +361,7 @@ struct WSPlan {
 bool ws_plan(int mode, int cin, int cout, WSPlan& pl, bool f32 = false) {
   // (fp32 inference forward, up6-up8: 0.61-0.69 -> 0.79-0.80 of fp32 peak against the
   // implicit GEMM, 1080p b8 fp32 inference 94.3 -> 95.9 frames/s, profiles/r03zp_*)
-  if (cout % 32 || cin % 32) return false;
+  if (cout % 32 || cin % 32 || cout <= 0 || cin <= 0) return false;
   // the bf16 input gradient (up8, K = 512) runs on igemm_fwd2p_kernel: 1.52 -> 1.31 ms
   // (profiles/r05/r05t2_ab_up8_dgrad_fwd2p.txt)
   if (mode == 1 && !f32) return false;

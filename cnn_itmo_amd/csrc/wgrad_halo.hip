@@ -606,6 +606,7 @@ struct WHPlan {
 };
 
 bool wh_plan(int n, int h, int w, int cin, int cout, WHPlan& pl, bool cat = false) {
+  if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return false;  // nothing to launch
   pl.bm = cout % 64 == 0 ? 64 : (cout == 32 ? 32 : 0);
   pl.bn = cin % 96 == 0 ? 96 : (cin % 64 == 0 ? 64 : (cin % 32 == 0 ? 32 : 0));
   if (!cat && cout % 64 == 0 && cin % 128 == 0) pl.bn = 128;
@@ -669,6 +670,7 @@ void wh_launch(const WHArgs& a, unsigned grid, hipStream_t s) {
 // fp32 plan: 32 / 64 x 32 / 64 blocks (64 x 96 for cin 96), 64-pixel strips, the row split of
 // wh_plan's policy
 bool wh_plan_f32(int n, int h, int w, int cin, int cout, WHPlan& pl) {
+  if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return false;  // nothing to launch
   pl.bm = cout % 64 == 0 ? 64 : (cout % 32 == 0 ? 32 : 0);
   pl.bn = cin % 64 == 0 ? 64 : (cin % 32 == 0 ? 32 : 0);
   if (WF_BN96 && pl.bm == 64 && cin % 96 == 0 && cin % 64 != 0) pl.bn = 96;

@@ -211,6 +211,7 @@ struct WTPlan {
 };
 
 bool wt_plan(int n, int h, int w, int cin, int cout, WTPlan& pl) {
+  if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return false;  // nothing to launch
   pl.bm = cout % 128 == 0 ? 128 : (cout % 64 == 0 ? 64 : 0);
   pl.bn = cin % 128 == 0 ? 128 : 0;
   if (!pl.bm || !pl.bn) return false;
@@ -406,6 +407,7 @@ __global__ __launch_bounds__(WTF_NW * 64) void wgrad_tconv_f32_kernel(const WTFA
 
 // row split for the fp32 kernel: the bf16 plan's policy at one 120 KB workgroup per CU
 bool wtf_plan(int n, int h, int w, int cin, int cout, WTPlan& pl) {
+  if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return false;  // nothing to launch
   if (cout % WTF_BM || cin % WTF_BN) return false;
   pl.bm = WTF_BM;
   pl.bn = WTF_BN;

@@ -15,6 +15,10 @@
  *     caller-owned; size it with the *_workspace_bytes / *_rows queries.
  *   - Return value: 0 = ok, negative = error (CNNITMO_E*);
  *     cnnitmo_last_error() returns a thread-local message.
+ *   - The size queries (*_rows, *_workspace_bytes, *_supported, *_kernel_name) run
+ *     on the host and need no GPU.  For sizes no launch takes (a channel count of 0
+ *     or one that is no multiple of what the kernels need, no pixels) they answer
+ *     0 rows, 0 bytes, 0 or "" -- the launch itself then returns CNNITMO_EINVAL.
  *   - dtype: CNNITMO_F32 (fp32 storage) or CNNITMO_BF16 (bf16 storage).
  *     Accumulation is always fp32 (MFMA f32 accumulators).
  *   - Activations are NHWC.  A "view" of an activation is (ptr, ld, off):

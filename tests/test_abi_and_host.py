@@ -197,6 +197,90 @@ def test_tconv_planner_choices(lib):
     assert name(0, 8, 272, 480, 256, 128, 0).startswith(b"tconv_ws_kernel<f32")  # fp32: unchanged
 
 
+def run_child(mode, env=None, timeout=120):
+    """One fresh python running tests/host_query_child.py <mode>; it prints every call before
+    making it, so after an abnormal exit the last line names the call that killed it."""
+    import subprocess
+    import sys
+    child = os.path.join(ROOT, "tests", "host_query_child.py")
+    r = subprocess.run([sys.executable, child, mode], capture_output=True, text=True, timeout=timeout,
+                       env=dict(os.environ, **(env or {})))
+    lines = r.stdout.strip().splitlines()
+    last = lines[-1] if lines else "(no output)"
+    assert r.returncode == 0, f"child ended with status {r.returncode} at: {last}\n{r.stderr[-3000:]}"
+    return lines
+
+
+def test_host_queries_never_kill_the_process(lib):
+    """Every host-only query of the ABI (*_rows, *_workspace_bytes, *_supported, *_kernel_name) over
+    channel counts from 0 up, three frame sizes, both dtypes, 1 / 4 / 9 taps: an unsupported size
+    gives 0 bytes, 0 rows or "" -- never a signal (w2_plan's and make_plan's division by zero
+    tiles ended the process with SIGFPE for channel counts below 32)."""
+    lines = run_child("sweep")
+    assert lines[-1].startswith("done ") and int(lines[-1].split()[1]) > 15000, lines[-1]
+
+
+def test_wgrad_launches_refuse_small_channel_counts(lib):
+    """cnnitmo_conv_wgrad / cnnitmo_tconv2x2_wgrad with channel counts below 32 (or 0): a negative
+    status and a message, from the host checks that precede every launch."""
+    lines = run_child("launch")
+    assert lines[-1].startswith("done ") and int(lines[-1].split()[1]) > 0, lines[-1]
+
+
+def test_dispatch_coverage(lib):
+    """Every kernel the planners choose anywhere in the documented domain (tests/kernel_cases.py:
+    DOMAIN_CH x DOMAIN_CH x DOMAIN_HW, both dtypes, and the 3x3 conv again with CNNITMO_HALO=0) is
+    the kernel of some case of the GPU tests' shared lists.  No allow-list: a newly reachable
+    kernel needs a case."""
+    import json
+    from tests import kernel_cases as KC
+    worlds = [json.loads(run_child("names")[-1]), json.loads(run_child("names", env={"CNNITMO_HALO": "0"})[-1])]
+    reach, test = {}, {}
+    for w in worlds:
+        reach.update(w["reachable"])
+        test.update(w["tested"])
+    assert len(reach) > 90 and any(k.startswith(KC.HALO0 + "igemm_fwd") for k in reach), sorted(reach)
+    print("kernel name | reached in the domain first at | case that launches it")
+    for k in sorted(reach):
+        print(f"{k} | {reach[k]} | {test.get(k, 'NONE')}")
+    missing = {k: reach[k] for k in reach if k not in test}
+    assert not missing, f"kernels no shared case launches: {missing}"
+
+
+def test_case_lists_name_their_kernels(lib):
+    """The name written next to each shared case is what the planner answers (the GPU tests
+    assert the same before each launch; here without a GPU), and the fused dgrad's store path
+    table agrees with launch_cfg's condition restated from those names."""
+    from tests import kernel_cases as KC
+    from cnn_itmo_amd import _lib
+    q = _lib.query
+    for cases, namer in ((KC.CONV3X3_OPS, KC.conv3x3_names), (KC.CONV3X3_FOLD, KC.conv3x3_names),
+                         (KC.CONV3X3_ARENA, KC.conv3x3_names), (KC.TCONV_OPS, KC.tconv_names),
+                         (KC.TCONV_ARENA, KC.tconv_names), (KC.TCONV_FOLD, KC.tconv_names),
+                         (KC.TCONV_AFFINE, KC.tconv_names)):
+        for sh, exp in cases.items():
+            for dt in ("bf16", "f32"):
+                got = namer(q, dt, *sh)
+                assert all(e is None or e == g for e, g in zip(exp[dt], got)), (sh, dt, got, exp[dt])
+    for (cin, cout, h, w, c0, c1, _par), exp in KC.DGRAD_BN.items():
+        for dt in ("bf16", "f32"):
+            assert KC.dgrad_bn_name(q, dt, cin, cout, h, w, c0, c1) == exp[dt], (cin, cout, h, w, c0, c1, dt)
+    for sh, exp in KC.DGRAD_BN_POOLED.items():
+        for dt in ("bf16", "f32"):
+            assert KC.dgrad_bn_pooled_name(q, dt, *sh) == exp[dt], (sh, dt)
+    for sh, exp in KC.TCONV_DGRAD_BN.items():
+        assert KC.tconv_dgrad_bn_name(q, "bf16", *sh) == exp, sh
+    for (kind, cin, cout, h, w, c0, c1), exp in KC.DGRAD_BN_ORACLE.items():
+        got = (KC.dgrad_bn_name(q, "bf16", cin, cout, h, w, c0, c1) if kind == "c3"
+               else KC.tconv_dgrad_bn_name(q, "bf16", cin, cout, h, w))
+        assert got == exp, (kind, cin, cout, h, w, c0, c1, got)
+    by_shape = {(k[0], k[1], k[4], k[5]): (k, v) for k, v in KC.DGRAD_BN.items()}
+    assert len(KC.DGRAD_BN_BRANCH) >= 3 and set(KC.DGRAD_BN_BRANCH.values()) == {"all", "mixed", "neither"}
+    for (cin, cout, c0, c1, dt), branch in KC.DGRAD_BN_BRANCH.items():
+        case, names = by_shape[(cin, cout, c0, c1)]  # every row is a case the GPU tests launch
+        assert KC.dgrad_bn_branch(names[dt], dt, cin, c0, c1) == branch, (case, dt, names[dt])
+
+
 def test_halo_global_accesses_inside_their_tensors():
     """tools/check_halo_bounds.py: every in-range raw-buffer access of the shipped halo conv
     (patch and weight pieces, epilogue stores, the fused BN backward's r loads and pool route) of

@@ -61,6 +61,8 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import ref_objectives as RO  # noqa: E402
+import kernel_cases as KC  # noqa: E402
+from kernel_cases import expect_kernels  # noqa: E402
 from arena import Arena, bits, poison_count  # noqa: E402
 from launch_check import LaunchChecker  # noqa: E402
 
@@ -148,10 +150,7 @@ def rnd(a, T):
 
 
 # ---- Conv2D 3x3 ------------------------------------------------------------------------------
-CONV_SHAPES = [(32, 32, 5, 7),       # one partial 16 x 32 tile; resident weights
-               (96, 64, 18, 35),     # last tile partial in both directions; streamed weights
-               (64, 128, 16, 32),    # one whole tile, two column blocks
-               (256, 128, 10, 70)]   # streamed weights, partial last strip, 128-deep wgrad blocks
+CONV_SHAPES = list(KC.CONV3X3_ARENA)
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -159,6 +158,7 @@ CONV_SHAPES = [(32, 32, 5, 7),       # one partial 16 x 32 tile; resident weight
 def test_conv3x3(dt, cin, cout, H, W):
     from cnn_itmo_amd import _lib as L
     from cnn_itmo_amd import ops
+    expect_kernels(KC.conv3x3_names(L.query, dt, cin, cout, H, W), KC.CONV3X3_ARENA[(cin, cout, H, W)][dt])
 
     def body(r):
         rng = np.random.default_rng(cin + cout)
@@ -313,14 +313,14 @@ def test_cat(H, W):
     run_case("bf16", body, ["conv3x3_fwd_cat", "conv_wgrad_cat"])
 
 
-@pytest.mark.parametrize("cin,cout,H,W,c0,c1,par", [
-    (32, 32, 20, 40, 0, 32, False), (96, 64, 18, 70, 32, 96, True), (160, 64, 16, 40, 32, 160, True),
-    (192, 128, 16, 32, 64, 192, True), (128, 64, 17, 33, 0, 128, False)])
+@pytest.mark.parametrize("cin,cout,H,W,c0,c1,par", list(KC.DGRAD_BN))
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 def test_conv3x3_dgrad_bn(cin, cout, H, W, c0, c1, par, dt):
     """The columns [c0, c1) leave through the producer's BN backward (dz_out, part); dx gets the
     others only: its columns [c0, c1) are NOT payload."""
+    from cnn_itmo_amd import _lib as L
     from cnn_itmo_amd import ops
+    expect_kernels(KC.dgrad_bn_name(L.query, dt, cin, cout, H, W, c0, c1), KC.DGRAD_BN[(cin, cout, H, W, c0, c1, par)][dt])
 
     def body(r):
         rng = np.random.default_rng(cin + c0 + H)
@@ -352,10 +352,12 @@ def test_conv3x3_dgrad_bn(cin, cout, H, W, c0, c1, par, dt):
     run_case(dt, body, ["conv3x3_dgrad_bn", "colsum"])
 
 
-@pytest.mark.parametrize("cin,cout,H,W", [(32, 64, 20, 40), (32, 64, 34, 70), (64, 128, 16, 32), (32, 96, 18, 66)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.DGRAD_BN_POOLED))
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 def test_conv3x3_dgrad_bn_pooled(cin, cout, H, W, dt):
+    from cnn_itmo_amd import _lib as L
     from cnn_itmo_amd import ops
+    expect_kernels(KC.dgrad_bn_pooled_name(L.query, dt, cin, cout, H, W), KC.DGRAD_BN_POOLED[(cin, cout, H, W)][dt])
 
     def body(r):
         rng = np.random.default_rng(cin + cout + H + W)
@@ -383,15 +385,14 @@ def test_conv3x3_dgrad_bn_pooled(cin, cout, H, W, dt):
 
 
 # ---- Conv2DTranspose 2x2 ---------------------------------------------------------------------
-TCONV_SHAPES = [(64, 32, 3, 5),       # generic kernels
-                (128, 64, 3, 70), (128, 32, 2, 130),   # streamed (bf16), partial 64-pixel tiles
-                (256, 128, 7, 9), (512, 512, 3, 7),    # weight-stationary (bf16)
-                (512, 256, 5, 7)]     # the persistent 256 x 256 kernels
+TCONV_SHAPES = list(KC.TCONV_ARENA)
 
 
-@pytest.mark.parametrize("cin,cout,H,W", [(128, 64, 3, 70), (64, 32, 4, 64), (128, 32, 2, 130)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.TCONV_DGRAD_BN))
 def test_tconv_dgrad_bn(cin, cout, H, W):
+    from cnn_itmo_amd import _lib as L
     from cnn_itmo_amd import ops
+    expect_kernels(KC.tconv_dgrad_bn_name(L.query, "bf16", cin, cout, H, W), KC.TCONV_DGRAD_BN[(cin, cout, H, W)])
 
     def body(r):
         rng = np.random.default_rng(cin + W)
@@ -420,6 +421,7 @@ def test_tconv_dgrad_bn(cin, cout, H, W):
 def test_tconv(dt, cin, cout, H, W):
     from cnn_itmo_amd import _lib as L
     from cnn_itmo_amd import ops
+    expect_kernels(KC.tconv_names(L.query, dt, cin, cout, H, W), KC.TCONV_ARENA[(cin, cout, H, W)][dt])
 
     def body(r):
         rng = np.random.default_rng(cin)

@@ -10,7 +10,8 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from oracle import unet_ref as R  # noqa: E402
-from tests.test_gpu_ops import DT, TDT, close, dev, host, nans, rnd  # noqa: E402
+from tests import kernel_cases as KC  # noqa: E402
+from tests.test_gpu_ops import DT, TDT, close, dev, expect_kernels, host, nans, rnd  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -33,11 +34,11 @@ def affine(rng, c, neg=False):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("cin,cout,H,W", [(32, 32, 8, 12), (64, 128, 5, 7), (96, 64, 1, 6), (32, 64, 6, 1),
-                                          (128, 256, 3, 4), (64, 64, 8, 64), (32, 96, 4, 128),
-                                          (64, 64, 16, 96), (32, 32, 16, 128)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.CONV3X3_FOLD))
 def test_conv3x3_folded_fwd_wgrad(dt, cin, cout, H, W):
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
+    expect_kernels(KC.conv3x3_names(L.query, dt, cin, cout, H, W), KC.CONV3X3_FOLD[(cin, cout, H, W)][dt])
     rng = np.random.default_rng(cin * 7 + cout + H)
     N, ld, off = 2, cin + 32, 32  # r lives in a concat slice
     rb = np.maximum(rng.standard_normal((N, H, W, ld)), 0).astype(np.float32)
@@ -81,10 +82,11 @@ def test_conv3x3_folded_fwd_wgrad(dt, cin, cout, H, W):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("cin,cout,H,W", [(64, 32, 3, 5), (128, 64, 4, 4), (512, 256, 2, 3)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.TCONV_FOLD))
 def test_tconv_folded_fwd_wgrad(dt, cin, cout, H, W):
     from cnn_itmo_amd import ops
     from cnn_itmo_amd import _lib as L
+    expect_kernels(KC.tconv_names(L.query, dt, cin, cout, H, W), KC.TCONV_FOLD[(cin, cout, H, W)][dt])
     rng = np.random.default_rng(cin + 11)
     N = 2
     r = np.maximum(rng.standard_normal((N, H, W, cin)), 0).astype(np.float32)
@@ -251,12 +253,7 @@ def test_pool_deferred_route_and_sums(dt, H, W):
     np.testing.assert_allclose(host(db_a), host(db_b), rtol=tol, atol=tol * 20)
 
 
-@pytest.mark.parametrize("cin,cout,H,W,c0,c1,par", [
-    (32, 32, 20, 40, 0, 32, False),      # the whole input (enc1a -> enc1b), partial tiles
-    (96, 64, 18, 70, 32, 96, True),      # concat [skip 32 | up 64] -> BN 48 blocks (6 of 8 lanes)
-    (160, 64, 16, 40, 32, 160, True),    # BN 32 blocks
-    (192, 128, 16, 32, 64, 192, True),   # concat [skip 64 | up 128] -> BN 64 blocks
-    (128, 64, 17, 33, 0, 128, False)])
+@pytest.mark.parametrize("cin,cout,H,W,c0,c1,par", list(KC.DGRAD_BN))
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 def test_conv3x3_dgrad_bn_fused(cin, cout, H, W, c0, c1, par, dt):
     """cnnitmo_conv3x3_dgrad_bn == conv3x3_dgrad followed by bn_bwd_apply on the
@@ -265,6 +262,7 @@ def test_conv3x3_dgrad_bn_fused(cin, cout, H, W, c0, c1, par, dt):
     fp32 fused epilogue (fp32 training, 16-channel chunks)."""
     from cnn_itmo_amd import ops
     from cnn_itmo_amd import _lib as L
+    expect_kernels(KC.dgrad_bn_name(L.query, dt, cin, cout, H, W, c0, c1), KC.DGRAD_BN[(cin, cout, H, W, c0, c1, par)][dt])
     rng = np.random.default_rng(cin + c0 + H)
     N, d, c = 2, DT[dt], c1 - c0
     T = TDT[dt]
@@ -312,11 +310,7 @@ def test_conv3x3_dgrad_bn_fused(cin, cout, H, W, c0, c1, par, dt):
         assert np.isnan(gx[:, c0:c1]).all()  # fused columns are not written to dx
 
 
-@pytest.mark.parametrize("cin,cout,H,W", [
-    (32, 64, 20, 40),     # dec9's skip path (conv1 32 of the [32 | 64] concat), partial tiles
-    (32, 64, 34, 70),     # ragged in both directions (partial 16-row tiles, 32-column strips)
-    (64, 128, 16, 32),    # BN 64 (a level-1 skip path)
-    (32, 96, 18, 66)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.DGRAD_BN_POOLED))
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 def test_conv3x3_dgrad_bn_pooled(cin, cout, H, W, dt):
     """cnnitmo_conv3x3_dgrad_bn_pooled == conv3x3_dgrad of the skip rows, then
@@ -324,6 +318,8 @@ def test_conv3x3_dgrad_bn_pooled(cin, cout, H, W, dt):
     the same coefficients: the deferred skip gradient of dec9 fused with conv1's
     MaxPooling2D route and BN backward."""
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
+    expect_kernels(KC.dgrad_bn_pooled_name(L.query, dt, cin, cout, H, W), KC.DGRAD_BN_POOLED[(cin, cout, H, W)][dt])
     rng = np.random.default_rng(cin + cout + H + W)
     N, d = 2, DT[dt]
     T = TDT[dt]
@@ -368,10 +364,12 @@ def test_conv3x3_dgrad_bn_pooled(cin, cout, H, W, dt):
     np.testing.assert_allclose(host(sf), host(sref), rtol=1e-4, atol=1e-2)
 
 
-@pytest.mark.parametrize("cin,cout,H,W", [(128, 64, 3, 70), (64, 32, 4, 64), (128, 32, 2, 130)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.TCONV_DGRAD_BN))
 def test_tconv_dgrad_bn_fused(cin, cout, H, W):
     """cnnitmo_tconv2x2_dgrad_bn == tconv2x2_dgrad followed by bn_bwd_apply (r from a view)."""
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
+    expect_kernels(KC.tconv_dgrad_bn_name(L.query, "bf16", cin, cout, H, W), KC.TCONV_DGRAD_BN[(cin, cout, H, W)])
     rng = np.random.default_rng(cin + W)
     N, d = 2, DT["bf16"]
     k = (rng.standard_normal((2, 2, cout, cin)) * 0.1).astype(np.float32)
@@ -406,17 +404,17 @@ def test_tconv_dgrad_bn_fused(cin, cout, H, W):
     np.testing.assert_allclose(host(sf), host(sref), rtol=1e-4, atol=1e-2)
 
 
-@pytest.mark.parametrize("kind,cin,cout,H,W,c0,c1", [
-    ("c3", 96, 64, 18, 70, 32, 96),     # dec9-style concat [skip 32 | up 64]
-    ("c3", 64, 64, 16, 64, 0, 64),      # whole input (enc chain)
-    ("c3", 192, 128, 16, 32, 64, 192),  # dec8-style
-    ("t2", 128, 64, 3, 70, 0, 128)])    # up9 dgrad into conv8's BN
+@pytest.mark.parametrize("kind,cin,cout,H,W,c0,c1", list(KC.DGRAD_BN_ORACLE))
 def test_dgrad_bn_fused_vs_oracle(kind, cin, cout, H, W, c0, c1):
     """The fused dgrad + producer-BN-backward pinned DIRECTLY to the oracle:
     R.conv2d_same_bwd / R.tconv2x2s2_bwd for g, then R.bn_train_bwd and the ReLU
     mask for the producer's dz.  Coefficients come from the product's
     cnnitmo_bn_bwd_finalize fed the oracle's sums (sum dy, sum dy*rhat)."""
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
+    expect_kernels(KC.dgrad_bn_name(L.query, "bf16", cin, cout, H, W, c0, c1) if kind == "c3"
+                   else KC.tconv_dgrad_bn_name(L.query, "bf16", cin, cout, H, W),
+                   KC.DGRAD_BN_ORACLE[(kind, cin, cout, H, W, c0, c1)])
     rng = np.random.default_rng(cin + cout + H)
     N, d, c = 2, DT["bf16"], c1 - c0
     ho, wo = (H, W) if kind == "c3" else (2 * H, 2 * W)

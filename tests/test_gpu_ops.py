@@ -12,6 +12,8 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from oracle import unet_ref as R  # noqa: E402
+from tests import kernel_cases as KC  # noqa: E402
+from tests.kernel_cases import expect_kernels  # noqa: E402
 
 DT = {"f32": 0, "bf16": 1}
 TDT = {"f32": torch.float32, "bf16": torch.bfloat16}
@@ -51,17 +53,19 @@ def close(got, want, dt, what=""):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("cin,cout,H,W", [(32, 32, 8, 12), (64, 128, 5, 7), (96, 64, 6, 10), (32, 256, 4, 4),
-                                          # whole 4x64 tiles: the halo kernel (bf16) for fwd and dgrad
-                                          (32, 32, 8, 64), (96, 64, 4, 128), (192, 128, 4, 64),
-                                          (64, 64, 12, 64), (32, 64, 12, 192), (96, 64, 16, 128),
-                                          (192, 128, 8, 64), (64, 64, 16, 64), (32, 64, 24, 192),
-                                          # 128-channel-deep wgrad blocks, a partial last strip
-                                          (128, 64, 6, 64), (256, 128, 10, 70)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.CONV3X3_OPS))
 def test_conv3x3_fwd_dgrad_wgrad(dt, cin, cout, H, W):
+    conv3x3_case(dt, cin, cout, H, W, KC.CONV3X3_OPS[(cin, cout, H, W)][dt])
+
+
+def conv3x3_case(dt, cin, cout, H, W, names):
+    """Forward (ReLU + BN sums), input gradient and weight gradient of one 3x3 conv against the
+    oracle; names: the (forward, input gradient, weight gradient) kernels the case is meant for."""
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
     rng = np.random.default_rng(cin + cout)
-    N = 2
+    N = KC.N
+    expect_kernels(KC.conv3x3_names(L.query, dt, cin, cout, H, W), names)
     # input lives in a wider buffer (zero-copy concat view): ld = cin + 32, off = 32
     ld, off = cin + 32, 32
     xb = rng.standard_normal((N, H, W, ld)).astype(np.float32)
@@ -123,9 +127,17 @@ def test_conv3x3_halo_tall_frame():
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("H,W", [(6, 9), (4, 64)])
 def test_conv_affine_inference_epilogue(dt, H, W):
+    affine_epilogue_case(dt, H, W)
+
+
+def affine_epilogue_case(dt, H, W, cin=32, cout=64, name=None):
+    """The inference forward: ReLU, then the BN affine, no sums; name: the kernel it is meant for."""
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
     rng = np.random.default_rng(3)
-    N, cin, cout = 1, 32, 64
+    N = 1
+    if name is not None:
+        expect_kernels(KC.conv3x3_names(L.query, dt, cin, cout, H, W, N)[0], name)
     x = rng.standard_normal((N, H, W, cin)).astype(np.float32)
     w = (rng.standard_normal((cout, 3, 3, cin)) * 0.1).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
@@ -143,24 +155,13 @@ def test_conv_affine_inference_epilogue(dt, H, W):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("cin,cout,H,W", [(64, 32, 3, 5), (128, 64, 4, 4), (512, 256, 2, 3),
-                                          # bf16: the streamed kernel (resident weights), partial 64-px tiles
-                                          (128, 64, 3, 70), (256, 128, 5, 33), (128, 32, 2, 130),
-                                          # bf16 weight-stationary kernel: fwd at 32 column blocks
-                                          # (512 -> 512), dgrad at BN 128 (256 <- 128); ragged tiles
-                                          (512, 512, 3, 7), (256, 128, 7, 9),
-                                          # 1024 / 2048-deep gradients (up7 / up6: igemm_fwd2p's
-                                          # persistent 256 x 256 tiles; ragged tiles)
-                                          (512, 256, 5, 7), (512, 256, 17, 33), (256, 512, 9, 31),
-                                          # > 256 tiles of 256 x 256: each persistent workgroup
-                                          # (igemm_fwd2p_kernel, one per CU) walks several
-                                          (512, 256, 96, 176),
-                                          # bf16 row-streaming wgrad: 4 rows per workgroup, 2 strips
-                                          (512, 512, 16, 40)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.TCONV_OPS))
 def test_tconv(dt, cin, cout, H, W):
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
     rng = np.random.default_rng(cin)
-    N = 2
+    N = KC.N
+    expect_kernels(KC.tconv_names(L.query, dt, cin, cout, H, W), KC.TCONV_OPS[(cin, cout, H, W)][dt])
     x = rng.standard_normal((N, H, W, cin)).astype(np.float32)
     k = (rng.standard_normal((2, 2, cout, cin)) * 0.1).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
@@ -197,14 +198,16 @@ def test_tconv(dt, cin, cout, H, W):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("cin,cout,H,W", [(512, 256, 5, 7), (256, 128, 9, 40)])
+@pytest.mark.parametrize("cin,cout,H,W", list(KC.TCONV_AFFINE))
 def test_tconv_affine_inference_epilogue(dt, cin, cout, H, W):
     """Conv2DTranspose forward with the inference BN affine after the ReLU (no sums): bf16 runs
     tconv_fwd2p_kernel, whose plan depends on the sizes only (the stat-row query matches
     whatever flags the launch carries)."""
     from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
     rng = np.random.default_rng(cin + 1)
-    N = 2
+    N = KC.N
+    expect_kernels(KC.tconv_names(L.query, dt, cin, cout, H, W), KC.TCONV_AFFINE[(cin, cout, H, W)][dt])
     x = rng.standard_normal((N, H, W, cin)).astype(np.float32)
     k = (rng.standard_normal((2, 2, cout, cin)) * 0.1).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
@@ -269,6 +272,28 @@ def test_first_layer_im2col(dt):
     ops.conv_wgrad(d, 1, ops.View(cols, N, H, W, 32, 32), dev(dz, dt), 32, dw, dw_cols=27)
     torch.cuda.synchronize()
     close(host(dw).reshape(dw_ref.shape), dw_ref, dt, "first layer wgrad")
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_conv1tap_wgrad_128(dt):
+    """cnnitmo_conv_wgrad with one tap, 128 -> 128 channels: the sizes at which bf16 runs the first
+    implicit-GEMM weight gradient, igemm_wgrad_kernel<bf16,128,128> (igemm_wgrad2 has no 128 x 128
+    tile, and with 9 or 4 taps the row-streaming kernels take these channel counts).  x is a slice
+    of a wider buffer; 306 pixels: several K steps, the last one partial."""
+    from cnn_itmo_amd import ops
+    from cnn_itmo_amd import _lib as L
+    rng = np.random.default_rng(128)
+    N, H, W, c, ld, off = 2, 9, 17, 128, 160, 32
+    d = DT[dt]
+    name = L.query("cnnitmo_wgrad_kernel_name", d, 1, N, H, W, c, c).decode()
+    assert name == f"igemm_wgrad_kernel<{dt},128,128>", name
+    xb = rng.standard_normal((N, H, W, ld)).astype(np.float32)
+    dz = rng.standard_normal((N, H, W, c)).astype(np.float32)
+    dw_ref = rnd(dz, dt).reshape(-1, c).T @ rnd(xb, dt)[..., off:].reshape(-1, c)
+    dw = nans((c, c))
+    ops.conv_wgrad(d, 1, ops.View(dev(xb, dt).reshape(-1), N, H, W, c, ld, off), dev(dz, dt), c, dw)
+    torch.cuda.synchronize()
+    close(host(dw), dw_ref, dt, "one-tap wgrad")
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
@@ -577,3 +602,24 @@ def test_conv3x3_fwd_cat_dec9(H, W):
     s = st.view(rows, 2, 64).double().sum(0).cpu().numpy()
     serr = float(np.abs(s[0] - got.reshape(-1, 64).sum(0)).max()) / max(1.0, float(np.abs(got).sum()))
     assert err <= 1.5e-2 and serr <= 1e-5, (err, serr)
+
+
+def test_conv3x3_without_halo_kernel():
+    """CNNITMO_HALO=0, the supported switch for A/B runs of the halo kernel and the path of every
+    shape halo_plan refuses: the 9-tap implicit GEMMs (igemm_fwd_kernel, igemm_fwd2_kernel) at this
+    file's bounds for the forward, input gradient and inference epilogue, and a whole training step
+    at test_unet_train_step_parity's.  The variable is read once per process: one fresh child
+    (tests/halo0_child.py), which stops at its first failure."""
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.time()
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "halo0_child.py")], capture_output=True, text=True,
+                       env=dict(os.environ, CNNITMO_HALO="0"), timeout=600)
+    print(r.stdout[-6000:])
+    print(f"CNNITMO_HALO=0 child: {time.time() - t0:.1f} s")
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-4000:]
+    assert "halo0 child ok" in r.stdout
+    launched = [ln for ln in r.stdout.splitlines() if ln.startswith("conv3x3 ")]
+    assert len(launched) == 2 * len(KC.CONV3X3_HALO0) and all("fwd igemm_" in ln and "dgrad igemm_" in ln for ln in launched)
