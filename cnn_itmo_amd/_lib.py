@@ -144,6 +144,8 @@ SIGNATURES = {
     "cnnitmo_hdr_encode": (i32, [i32, vp, i32, i32, i32, vp, vp, vp]),
     "cnnitmo_lum_percentile_workspace_bytes": (i64, [i32]),
     "cnnitmo_lum_percentile": (i32, [vp, i32, i32, i32, vp, f64, vp, vp, i64, vp]),
+    "cnnitmo_jpeg_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "cnnitmo_jpeg_roundtrip": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
 }
 
 

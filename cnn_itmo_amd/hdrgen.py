@@ -27,6 +27,13 @@ and ``last_global_batch``.  Per frame of the global batch the draws are, from th
    as an offline tool can.  ``cameras='fixed'`` draws nothing: file j always gets element 0 of
    ``tonemap.virtual_camera_params(1, np.random.default_rng(seed + j))``, make_dataset's
    ``--cameras 1`` values (a seed of None counts as 0), so validation batches repeat every epoch.
+4. only with ``jpeg_quality`` set (the stream of a generator without it is unchanged):
+   ``u = random_sample()``, then for a range ``(lo, hi)`` the quality ``q = randint(lo, hi + 1)``,
+   drawn whether or not the frame is compressed, so the position of the stream does not depend on
+   outcomes; the frame is compressed iff ``u < jpeg_prob``.  With ``cameras='fixed'`` nothing is
+   drawn from the stream here either: file j takes ``u = random()`` and then, for a range,
+   ``q = integers(lo, hi + 1)`` from its own ``default_rng(seed + j)``, after the camera's values.
+   The draw's ``'jpeg'`` is the quality, 0 for a frame that is not compressed.
 
 The matrix handed to the kernel maps an output pixel to the source picture:
 ``M_src = T(top, left) . S . M_keras``, with ``M_keras`` the ``ImageDataGenerator.affine`` matrix at
@@ -35,6 +42,12 @@ identity when the window has the target size); the bilinear taps are clamped to 
 
 ``quantize``: ``'input'`` (default) rounds x to the 8-bit levels an SDR file has and leaves the
 target in fp32; ``'both'`` also rounds y (what the PNG route trains on); ``None`` rounds neither.
+
+``jpeg_quality``: ``None`` (default) leaves x as the camera made it; an int or an inclusive range
+``(lo, hi)`` of libjpeg qualities puts each input, with probability ``jpeg_prob``, through a
+baseline-JPEG round trip on the GPU (``degrade.jpeg_roundtrip``'s kernel, ``jpeg_subsampling``
+``'4:2:0'`` or ``'4:4:4'``), the compression the SDR material in the wild has been through.  The target
+y is never touched.  JPEG codes 8-bit samples, so ``quantize=None`` with it is a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -44,7 +57,7 @@ import re
 
 import numpy as np
 
-from . import hdrio
+from . import degrade, hdrio
 from .datagen import ImageDataGenerator, Iterator
 from .make_dataset import EXTENSIONS
 
@@ -93,7 +106,8 @@ class HDRPairGenerator:
     ``tonemap.reinhard`` / ``tonemap.virtual_camera``."""
 
     def __init__(self, rotation_range=0, zoom_range=0, horizontal_flip=False, vertical_flip=False, shear_range=0,
-                 width_shift_range=0, height_shift_range=0, key=0.18, lum=None, quantize="input", cameras="random"):
+                 width_shift_range=0, height_shift_range=0, key=0.18, lum=None, quantize="input", cameras="random",
+                 jpeg_quality=None, jpeg_prob=1.0, jpeg_subsampling="4:2:0"):
         if quantize not in QUANTIZE:
             raise ValueError(f"quantize {quantize!r}: 'input', 'both' or None")
         if cameras not in ("random", "fixed"):
@@ -105,6 +119,27 @@ class HDRPairGenerator:
         self.key = float(key)
         self.lum = None if lum is None else tuple(float(c) for c in lum)
         self.quantize, self.cameras = quantize, cameras
+        self.jpeg = None  # (lo, hi) qualities, inclusive
+        self.jpeg_range = bool(np.ndim(jpeg_quality))  # a range draws its quality, an int does not
+        if jpeg_quality is not None:
+            lo, hi = jpeg_quality if np.ndim(jpeg_quality) else (jpeg_quality, jpeg_quality)
+            self.jpeg = (degrade.check_quality(lo), degrade.check_quality(hi))
+            if self.jpeg[0] > self.jpeg[1]:
+                raise ValueError(f"jpeg_quality {jpeg_quality!r}: lo > hi")
+            if quantize is None:
+                raise ValueError("jpeg_quality needs 8-bit inputs: quantize 'input' or 'both', not None")
+        if not 0.0 <= jpeg_prob <= 1.0:
+            raise ValueError(f"jpeg_prob {jpeg_prob!r}: a probability in [0, 1]")
+        if jpeg_subsampling not in degrade.SUBSAMPLINGS:
+            raise ValueError(f"jpeg_subsampling {jpeg_subsampling!r}: '4:4:4' or '4:2:0'")
+        self.jpeg_prob, self.jpeg_subsampling = float(jpeg_prob), jpeg_subsampling
+
+    def jpeg_draw(self, uniform, integers):
+        """Step 4 of a frame's draws from the two given callables: the quality, 0 = not compressed."""
+        lo, hi = self.jpeg
+        u = uniform()
+        q = int(integers(lo, hi + 1)) if self.jpeg_range else lo
+        return q if u < self.jpeg_prob else 0
 
     def flow_from_directory(self, hdr_dir, target_size, window="random", window_size=None, batch_size=32,
                             shuffle=True, seed=None, cache=True, workers=8, rank=None, world=None, output="cuda"):
@@ -135,12 +170,15 @@ class HDRPairIterator(Iterator):
             for f, (hs, ws) in zip(self.filenames, self.sizes):
                 if hs < ch or ws < cw:
                     raise ValueError(f"{f}: a {hs} x {ws} picture is smaller than the {ch} x {cw} window")
-        self.fixed_cameras = None
+        self.fixed_cameras = self.fixed_jpeg = None
         if gen.cameras == "fixed":
             from .tonemap import virtual_camera_params
             base = 0 if seed is None else seed
-            self.fixed_cameras = [tuple(float(a[0]) for a in virtual_camera_params(1, np.random.default_rng(base + j)))
-                                  for j in range(len(names))]
+            self.fixed_cameras, self.fixed_jpeg = [], []
+            for j in range(len(names)):
+                own = np.random.default_rng(base + j)
+                self.fixed_cameras.append(tuple(float(a[0]) for a in virtual_camera_params(1, own)))
+                self.fixed_jpeg.append(gen.jpeg_draw(own.random, own.integers) if gen.jpeg else 0)
         self._sources = {}
         self._pool = cf.ThreadPoolExecutor(max_workers=workers)
         self.last_draws = None
@@ -150,7 +188,7 @@ class HDRPairIterator(Iterator):
     # ---- the random stream (host only) ----------------------------------------------------
     def _draw(self, index_array):
         """The draws of every frame of the global batch, in the documented order; returns this
-        rank's share as dicts (j, params, top, left, ch, cw, camera = (v, n, y))."""
+        rank's share as dicts (j, params, top, left, ch, cw, camera = (v, n, y), jpeg = quality or 0)."""
         h, w = self.target_size
         rng, draws = self.rng, []
         for j in index_array:
@@ -174,7 +212,12 @@ class HDRPairIterator(Iterator):
                 while y <= 0:
                     y = rng.normal(0.9, np.sqrt(0.1))
                 camera = (float(v), float(n), float(y))
-            draws.append({"j": j, "params": params, "top": top, "left": left, "ch": ch, "cw": cw, "camera": camera})
+            jpeg = 0
+            if self.gen.jpeg:
+                jpeg = self.fixed_jpeg[j] if self.fixed_jpeg is not None else \
+                    self.gen.jpeg_draw(rng.random_sample, rng.randint)
+            draws.append({"j": j, "params": params, "top": top, "left": left, "ch": ch, "cw": cw, "camera": camera,
+                          "jpeg": jpeg})
         lo, hi = self._local(len(draws))
         return draws[lo:hi]
 
@@ -231,6 +274,9 @@ class HDRPairIterator(Iterator):
         y = torch.empty_like(x)
         ops.hdr_pairs(d_desc, d_mats.view(torch.float64), d_flips.view(torch.int32), d_cam.view(torch.float64), x, y,
                       key=self.gen.key, lum=self.gen.lum, quantize=QUANTIZE[self.gen.quantize])
+        if any(d["jpeg"] for d in draws):  # in place, on x alone; the tables and the flags are host arrays
+            ops.jpeg_roundtrip(x, np.stack([degrade.quant_tables(d["jpeg"] or 50) for d in draws]),
+                               self.gen.jpeg_subsampling, apply=[d["jpeg"] for d in draws], out=x)
         if self.output == "numpy":
             return x.cpu().numpy(), y.cpu().numpy()
         return x, y

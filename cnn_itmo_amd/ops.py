@@ -677,3 +677,32 @@ def lum_percentile(img, q, lum=None, out=None):
     call("cnnitmo_lum_percentile", ptr(img), n, h, w, None if lc is None else ctypes.addressof(lc), float(q),
          ptr(out), ws.data_ptr(), ws.numel(), stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------- JPEG round trip
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:0": 1}
+
+
+def jpeg_workspace_bytes(n, h, w, subsampling):
+    return int(query("cnnitmo_jpeg_workspace_bytes", n, h, w, JPEG_SUBSAMPLINGS[subsampling]))
+
+
+def jpeg_roundtrip(x, qtabs, subsampling, apply=None, out=None, ws=None):
+    """x [n,h,w,3] contiguous fp32 device tensor -> out like x (may be x): the baseline-JPEG round
+    trip of uint8(255 x) (cnnitmo_jpeg_roundtrip).  qtabs: HOST uint16 [n,2,64] (numpy), natural order,
+    no entry 0; apply: HOST [n] (numpy, nonzero = compress, 0 = copy through), None = all;
+    subsampling: '4:4:4' or '4:2:0'."""
+    n, h, w, c = x.shape
+    assert c == 3 and x.dtype == torch.float32 and x.is_contiguous(), (x.dtype, tuple(x.shape))
+    qt = np.ascontiguousarray(qtabs, dtype=np.uint16)
+    assert qt.shape == (n, 2, 64), qt.shape
+    ap = None if apply is None else np.ascontiguousarray(np.asarray(apply) != 0, dtype=np.uint8)
+    assert ap is None or ap.shape == (n,), ap.shape
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
+    if ws is None:
+        ws = workspace(jpeg_workspace_bytes(n, h, w, subsampling), x.device)
+    call("cnnitmo_jpeg_roundtrip", ptr(x), n, h, w, JPEG_SUBSAMPLINGS[subsampling], qt.ctypes.data,
+         None if ap is None else ap.ctypes.data, ptr(out), ptr(ws), ws.numel(), stream_ptr())
+    return out

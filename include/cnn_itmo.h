@@ -65,7 +65,8 @@ extern "C" {
  * (new entry points only, nothing existing changed): cnnitmo_rgbe_encode / cnnitmo_rgbe_decode,
  * cnnitmo_hdr_pairs / cnnitmo_hdr_pairs_workspace_bytes, cnnitmo_hdr_encode,
  * cnnitmo_lum_percentile / cnnitmo_lum_percentile_workspace_bytes,
- * cnnitmo_grad_sumsq / cnnitmo_grad_sumsq_workspace_bytes / cnnitmo_grad_clip. */
+ * cnnitmo_grad_sumsq / cnnitmo_grad_sumsq_workspace_bytes / cnnitmo_grad_clip,
+ * cnnitmo_jpeg_roundtrip / cnnitmo_jpeg_workspace_bytes. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -763,6 +764,51 @@ int cnnitmo_hdr_encode(int encoding, const float* img, int n, int h, int w, cons
 long cnnitmo_lum_percentile_workspace_bytes(int n);
 int cnnitmo_lum_percentile(const float* img, int n, int h, int w, const double* lum_coef, double q, float* out,
                            void* workspace, long workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Baseline-JPEG round trip (encode + decode, no entropy coding: it is lossless) of n frames
+ * x [n][h][w][3] fp32 -> out, same shape: the degradation of an SDR input that went through a
+ * JPEG file.  Integers end to end after the load, the pixel path of the IJG library (libjpeg 6b /
+ * libjpeg-turbo, default settings) restated in int32; tests/jpeg_ref.py is the same in numpy and
+ * the two agree bit for bit.  `>>` is the arithmetic shift, clamp is to 0..255.  Per image:
+ *   1. u = uint8(255 x): round half away from zero, saturating, NaN -> 0 (the quantised store of
+ *      cnnitmo_hdr_pairs; exact for an x already on 8-bit levels).
+ *   2. Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16                       (jccolor.c)
+ *      Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *      Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   3. 4:2:0: chroma (i, j), i < ceil(h/2), = (the four full-resolution samples of rows
+ *      min(2i, h-1), min(2i+1, h-1) and columns min(2j, w-1), min(2j+1, w-1), + 1 for an even j,
+ *      + 2 for an odd j) >> 2, for every j up to a multiple of 8 (jcsample.c replicates the right
+ *      edge before it averages); rows are then added by replication.  4:4:4 skips this.
+ *   4. per plane: whole 8x8 blocks by edge replication, - 128, jfdctint.c's forward DCT (rows,
+ *      then columns; 8 x the coefficient), q = sign(c) ((|c| + (8Q >> 1)) / (8Q)), c' = q Q,
+ *      jidctint.c's inverse DCT (columns, then rows), + 128, clamp.  Q: qtabs[i][0] for Y,
+ *      qtabs[i][1] for Cb and Cr, natural (row-major) order.
+ *   5. 4:2:0: triangle upsampling over the ceil(h/2) x ceil(w/2) decoded chroma samples C,
+ *      neighbours replicated at the edges (jdsample.c, h2v2 "fancy"): output (r, c), i = r >> 1,
+ *      j = c >> 1, i' = i - 1 (r even) or i + 1 (r odd), j' likewise from c, both clamped;
+ *      s(j) = 3 C[i][j] + C[i'][j];  value = (3 s(j) + s(j') + (c odd ? 7 : 8)) >> 4.
+ *   6. cb = Cb - 128, cr = Cr - 128;  R = clamp(Y + ((91881 cr + 32768) >> 16)),       (jdcolor.c)
+ *      G = clamp(Y + ((-22554 cb - 46802 cr + 32768) >> 16)), B = clamp(Y + ((116130 cb + 32768) >> 16));
+ *      stored as (float)level * (float)(1/255.), cnnitmo_hdr_pairs' expression.
+ * subsampling: 0 = 4:4:4, 1 = 4:2:0.  qtabs: HOST array [n][2][64] (entries 1..65535; a libjpeg
+ * quality gives 1..255) and apply: HOST array [n], nullable = all 1; an image with apply 0 is
+ * copied through bit for bit.  Both are read before the call returns (they travel as kernel
+ * arguments, eight images per launch) and cost the same whether the images share a table or not.
+ * x, out: device, 4-byte aligned; the bits of out do not depend on any further alignment.  In
+ * place (out == x) is supported; any other overlap of the two is CNNITMO_EINVAL.  Every element
+ * of out is written exactly once.  workspace: cnnitmo_jpeg_workspace_bytes(n, h, w, subsampling)
+ * bytes of device memory, 8-byte aligned, contents irrelevant: the decoded planes as uint8, between
+ * the two launches of a group (1.5 or 3 bytes per pixel, each plane padded to whole blocks); the
+ * query needs no GPU and answers 0 for a shape the call refuses.  No atomics: bitwise reproducible.
+ * Stateless, never allocates.  CNNITMO_EINVAL before any launch: a null pointer (apply may be
+ * null), n, h or w < 1, h*w >= 2^29, h >= 2^21 - 64, subsampling outside 0..1, a table entry of 0,
+ * a short or misaligned workspace, a misaligned or partly overlapping x / out.
+ */
+long cnnitmo_jpeg_workspace_bytes(int n, int h, int w, int c /* chroma layout: the call's subsampling, 0 or 1 */);
+int cnnitmo_jpeg_roundtrip(const float* x, int n, int h, int w, int subsampling, const unsigned short* qtabs,
+                           const unsigned char* apply, float* out, void* workspace, long workspace_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }
