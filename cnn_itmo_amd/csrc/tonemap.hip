@@ -18,8 +18,9 @@
 // for 0/0, x/0, log(0) and min(1, NaN) = 1 (fmin).  imwrite's double -> uint8
 // (uint8(255*x): round half away from zero, saturate, NaN -> 0) is available as
 // the u8 output of the forward maps.  Sums are two-level and deterministic
-// (fixed block partition, fixed-order final fold); MATLAB's are sequential,
-// which differs only in the last bits.
+// (fixed block partition, fixed tree in each block and in the final fold);
+// MATLAB's are sequential, which differs only in the last bits.  max(., realmin)
+// keeps a NaN here, as the oracle's np.maximum does: a NaN pixel gives G = NaN.
 //
 // HBM-bound: 12 B read + 12 B (fp32) / 3 B (u8) written per pixel per map; the
 // statistics pass reads 12 B (fp32) or 3 B (u8) per pixel.
@@ -36,6 +37,10 @@ constexpr int BLK_PER_IMG = 256;  // blocks per image in the statistics pass
 
 __device__ __forceinline__ double decode_sdr(uint8_t v) { return pow((double)v / 255.0, 2.2); }
 
+// max(x, realmin) that keeps a NaN (fmax would drop it): a NaN pixel makes its image's log-average NaN,
+// as the oracle's np.maximum does
+__device__ __forceinline__ double at_least_realmin(double x) { return x < REALMIN ? REALMIN : x; }
+
 // mode 0: log(max(Y, realmin)) of an fp32 HDR image (Reinhard / virtual camera)
 // mode 1: log(max(X, realmin)), X = I/(I-1) of a uint8 SDR image (inverse_Reinhard.m as written)
 // stats per image: [sum of logs, count of zero luminance]
@@ -48,12 +53,12 @@ __global__ __launch_bounds__(TB) void stats_partial_kernel(int mode, const void*
     if (mode == 0) {
       const float* q = (const float*)img + ((long)im * hw + p) * 3;
       Y = lum(lc, q[0], q[1], q[2]);
-      s += log(fmax(Y, REALMIN));
+      s += log(at_least_realmin(Y));
     } else {
       const uint8_t* q = (const uint8_t*)img + ((long)im * hw + p) * 3;
       Y = lum(lc, decode_sdr(q[0]), decode_sdr(q[1]), decode_sdr(q[2]));
       const double X = Y / (Y - 1.0);
-      s += log(fmax(X, REALMIN));
+      s += log(at_least_realmin(X));
     }
     z += Y == 0.0 ? 1.0 : 0.0;
   }
@@ -75,16 +80,27 @@ __global__ __launch_bounds__(TB) void stats_partial_kernel(int mode, const void*
   }
 }
 
-__global__ void stats_final_kernel(const double* __restrict__ part, int n, double* __restrict__ stats) {
-  const int im = blockIdx.x * blockDim.x + threadIdx.x;
-  if (im >= n) return;
-  double s = 0.0, z = 0.0;
-  for (int b = 0; b < BLK_PER_IMG; ++b) {
-    s += part[((long)im * BLK_PER_IMG + b) * 2];
-    z += part[((long)im * BLK_PER_IMG + b) * 2 + 1];
+// One block per image folds its BLK_PER_IMG block sums with the same fixed tree as above.  (A sequential
+// fold of near-equal block sums rounds the same way at every step: 4e-15 of the sum for a constant image
+// of 256 x 256, where the tree is exact.)
+__global__ __launch_bounds__(BLK_PER_IMG) void stats_final_kernel(const double* __restrict__ part,
+                                                                  double* __restrict__ stats) {
+  const int im = blockIdx.x;
+  __shared__ double sh[2][BLK_PER_IMG];
+  sh[0][threadIdx.x] = part[((long)im * BLK_PER_IMG + threadIdx.x) * 2];
+  sh[1][threadIdx.x] = part[((long)im * BLK_PER_IMG + threadIdx.x) * 2 + 1];
+  __syncthreads();
+  for (int o = BLK_PER_IMG / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+    }
+    __syncthreads();
   }
-  stats[2 * im] = s;
-  stats[2 * im + 1] = z;
+  if (threadIdx.x == 0) {
+    stats[2 * im] = sh[0][0];
+    stats[2 * im + 1] = sh[1][0];
+  }
 }
 
 // curve 0: Reinhard; 1: virtual camera.  params per image: [key*2^v, n, y]
@@ -174,7 +190,7 @@ extern "C" int cnnitmo_tonemap_stats(int mode, const void* img, int n, int h, in
   const long hw = (long)h * w;
   hipLaunchKernelGGL(stats_partial_kernel, dim3(BLK_PER_IMG, n), dim3(TB), 0, s, mode, img, hw, lum_of(lum_coef),
                      (double*)workspace);
-  hipLaunchKernelGGL(stats_final_kernel, dim3((n + 63) / 64), dim3(64), 0, s, (const double*)workspace, n, stats);
+  hipLaunchKernelGGL(stats_final_kernel, dim3(n), dim3(BLK_PER_IMG), 0, s, (const double*)workspace, stats);
   return cnnitmo_check_launch("tonemap_stats");
 }
 

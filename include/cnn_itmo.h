@@ -551,7 +551,8 @@ int cnnitmo_augment_affine(int src_u8, const void* src, int n, int h, int w, int
  * luminance weights of RGB2Lum (not in the reference; NULL = Rec. 709).
  *   stats (device, [n][2]) = per image: sum of log(max(f, realmin)) over pixels,
  *   and the count of zero-luminance pixels; f = Y (mode 0, fp32 HDR input) or
- *   X = I/(I-1) (mode 1, uint8 SDR, inverse_Reinhard.m as written).
+ *   X = I/(I-1) (mode 1, uint8 SDR, inverse_Reinhard.m as written).  A NaN f
+ *   makes the image's sum NaN.  n <= 65535.
  *   apply: curve 0 = Reinhard, 1 = virtual camera; params (device, [n][3]) =
  *   (key*2^v, n, y) -- Reinhard uses (0.18, -, -); out fp32 or, out_u8 = 1,
  *   imwrite's uint8(255*x).  inverse: a = the key (0.18); mode 1 = the script

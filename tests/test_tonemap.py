@@ -98,7 +98,8 @@ def test_gpu_inverse_script_matches_oracle(gpu):
 
 @pytest.mark.gpu
 def test_gpu_exact_roundtrip_full_hd(gpu):
-    """Size-independent property at 1080p: the exact inverse undoes Reinhard."""
+    """Size-independent property at 1080p: the exact inverse undoes Reinhard.  It maps and inverts with
+    the same G, so it does not pin G: test_gpu_tonemap.py::test_log_average does."""
     rng = np.random.default_rng(5)
     hdr = _hdr(rng, 2, 1080, 1920)
     sdr = gpu.reinhard(hdr)
