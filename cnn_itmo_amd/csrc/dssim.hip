@@ -24,7 +24,7 @@
 // 4.6e-6 of max|dy| on a nearly flat pair (1/B2 ~ 1e3), outside the 1e-6 the tests hold.
 //
 // dssim_grad_kernel (pass 2): one workgroup owns TR x TC image rows x float-columns.  One plane
-// at a time it stages the (TR+10) x (TC+30) window of the plane above and to the left of its
+// at a time ssim_tile.h's adjoint_pass stages the (TR+10) x (TC+30) window of the plane above and to the left of its
 // tile (zero outside the map), runs the horizontal pass into fp64 row sums in LDS and the
 // vertical pass into registers: 27 KB of LDS instead of the 80 KB of three planes at once, at
 // the price of three rounds of barriers.  Each thread then holds Fa, Fb, Fc of 4 rows of one
@@ -32,8 +32,8 @@
 // base term's derivative and writes dy: every element of [n][h][w][3] exactly once.
 //
 // Numerics as in metrics.hip: fp64 after the loads, taps with explicit fma(), everything else
-// under `#pragma clang fp contract(off)`; per-workgroup sums, folded in a fixed order by
-// dssim_final_kernel.  No atomics: two runs are bitwise equal.  The two scale factors of dy
+// under `#pragma clang fp contract(off)`; per-workgroup sums, folded in a fixed order
+// (reduce.h) by dssim_final_kernel.  No atomics: two runs are bitwise equal.  The two scale factors of dy
 // are formed on the host, so a doubled grad_frames halves every product exactly.
 //
 // cnnitmo_rgb_accuracy: the head's 'accuracy' (argmax over RGB of prediction and target agree)
@@ -51,8 +51,7 @@
 
 namespace {
 
-using namespace ssim_tile;  // the tile, its staging and the separable fp64 filter of pass 1 (ssim_tile.h)
-static_assert((TR / G) * TC <= NT, "pass 2 keeps a thread's outputs in registers across the planes");
+using namespace ssim_tile;  // the tile, its staging and the separable fp64 filters of both passes (ssim_tile.h)
 
 // Pass 1.  part [n][nblk][2] = (sum of S, sum of the base term) of a tile; GRAD: planes
 // [n][3][mh][mw3] = (Pa, Pb, Pc) of every map element.  grid (tiles_x, tiles_y, n)
@@ -67,63 +66,13 @@ __global__ __launch_bounds__(NT) void dssim_coef_kernel(const float* __restrict_
 __global__ __launch_bounds__(NT) void dssim_grad_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                         const double* __restrict__ planes, int h, int w, int base,
                                                         Taps tp, double ks, double kb, float* __restrict__ dy) {
-  __shared__ double sp[IR][ICP];
-  __shared__ double hs[IR][TC];
-
   const int tid = threadIdx.x;
   const int w3 = 3 * w;
-  const int mh = h - 2 * R, mw3 = 3 * (w - 2 * R);
   const int r0 = blockIdx.y * TR, c0 = blockIdx.x * TC;
-  const long plane = (long)mh * mw3;
-  // the staged window's first map row / column: pixel (r, c) collects map rows r-10..r, columns c-30..c
-  const int q0 = r0 - 2 * R, p0 = c0 - 3 * 2 * R;
   const int rb = (tid / TC) * G, c = tid % TC;  // this thread's outputs: rows rb..rb+3 of column c (tid < 192)
 
   double f[3][G];
-#pragma unroll  // (f[k] stays in registers only with k a constant)
-  for (int k = 0; k < 3; ++k) {
-    const double* __restrict__ pk = planes + ((long)blockIdx.z * 3 + k) * plane;
-    for (int i = tid; i < IR * ICP; i += NT) {
-      const int r = i / ICP, cc = i % ICP;
-      const int qr = q0 + r, qc = p0 + cc;
-      double v = 0.0;
-      if (cc < IC && qr >= 0 && qr < mh && qc >= 0 && qc < mw3) v = pk[(long)qr * mw3 + qc];
-      sp[r][cc] = v;
-    }
-    __syncthreads();
-    // horizontal pass: staged column cb + 3m holds map column c0 + cb - 30 + 3m; output column
-    // cb + 3t takes it with tap g[10 - (m - t)]
-    for (int i = tid; i < IR * (TC / G); i += NT) {
-      const int r = i / (TC / G), gi = i % (TC / G);
-      const int cb = (gi / 3) * (3 * G) + gi % 3;
-      double acc[G];
-#pragma unroll
-      for (int t = 0; t < G; ++t) acc[t] = 0.0;
-#pragma unroll
-      for (int m = 0; m < GW; ++m) {
-        const double x = sp[r][cb + 3 * m];
-#pragma unroll
-        for (int t = 0; t < G; ++t)
-          if (m - t >= 0 && m - t < NTAP) acc[t] = fma(tp.g[NTAP - 1 - (m - t)], x, acc[t]);
-      }
-#pragma unroll
-      for (int t = 0; t < G; ++t) hs[r][cb + 3 * t] = acc[t];
-    }
-    __syncthreads();
-    // vertical pass into this thread's registers
-#pragma unroll
-    for (int t = 0; t < G; ++t) f[k][t] = 0.0;
-    if (tid < (TR / G) * TC) {
-#pragma unroll
-      for (int m = 0; m < GW; ++m) {
-        const double v = hs[rb + m][c];
-#pragma unroll
-        for (int t = 0; t < G; ++t)
-          if (m - t >= 0 && m - t < NTAP) f[k][t] = fma(tp.g[NTAP - 1 - (m - t)], v, f[k][t]);
-      }
-    }
-    __syncthreads();  // (sp and hs are written again for the next plane)
-  }
+  adjoint_pass(planes, h - 2 * R, 3 * (w - 2 * R), tp, f);
 
   if (tid >= (TR / G) * TC || c0 + c >= w3) return;
   const long img = (long)blockIdx.z * h * w3;
@@ -133,12 +82,8 @@ __global__ __launch_bounds__(NT) void dssim_grad_kernel(const float* __restrict_
     if (gr < h) {
       const long o = img + (long)gr * w3 + (c0 + c);
       const double y = (double)a[o], tg = (double)b[o];
-      const double d = y - tg;
-      double bd = 0.0;
-      if (base == CNNITMO_BASE_MSE) bd = 2.0 * d;
-      else if (base == CNNITMO_BASE_MAE) bd = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
       const double s = (f[0][t] + y * f[1][t]) + tg * f[2][t];
-      dy[o] = (float)(ks * s + kb * bd);
+      dy[o] = (float)(ks * s + kb * base_term_slope(base, y - tg));
     }
   }
 }
@@ -149,21 +94,7 @@ __global__ __launch_bounds__(NT) void dssim_final_kernel(const double* __restric
                                                          double n_pos, double alpha, double* __restrict__ out) {
   __shared__ double sh[2][NT];
   const int im = blockIdx.x;
-  double ss = 0.0, sq = 0.0;
-  for (long i = threadIdx.x; i < nblk; i += NT) {
-    ss += part[((long)im * nblk + i) * 2];
-    sq += part[((long)im * nblk + i) * 2 + 1];
-  }
-  sh[0][threadIdx.x] = ss;
-  sh[1][threadIdx.x] = sq;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  reduce::fold_tree_sum<2, NT>(part + (long)im * nblk * 2, nblk, sh);
   if (threadIdx.x == 0) {
     const double ssim = sh[0][0] / n_pos, bt = sh[1][0] / n_elem;
     out[3 * im] = ssim;
@@ -225,8 +156,8 @@ extern "C" int cnnitmo_dssim_loss_grad(int base, double alpha, const float* y, c
   const int mh = h - 2 * R, mw = w - 2 * R;
   const Taps tp = make_taps();
   const double c1 = 0.01 * 0.01, c2 = 0.03 * 0.03;
-  const dim3 grid((unsigned)((3L * mw + TC - 1) / TC), (unsigned)((mh + TR - 1) / TR), n);
-  const long nblk = (long)grid.x * grid.y;
+  const dim3 grid = map_grid(h, w, n);
+  const long nblk = tiles_of(h, w);
   double* part = (double*)workspace;
   double* planes = part + (long)n * nblk * 2;
   const bool vec = (3L * w) % 4 == 0 && aligned16(y) && aligned16(t);
@@ -239,9 +170,8 @@ extern "C" int cnnitmo_dssim_loss_grad(int base, double alpha, const float* y, c
     else COEF(false, true);
     const double frames = grad_frames > 0.0 ? grad_frames : (double)n;
     const double ks = -alpha / (frames * n_pos), kb = base == CNNITMO_BASE_NONE ? 0.0 : (1.0 - alpha) / (frames * n_elem);
-    const dim3 ggrid((unsigned)((3L * w + TC - 1) / TC), (unsigned)((h + TR - 1) / TR), n);
-    hipLaunchKernelGGL(dssim_grad_kernel, ggrid, dim3(NT), 0, s, y, t, (const double*)planes, h, w, base, tp, ks, kb,
-                       dy);
+    hipLaunchKernelGGL(dssim_grad_kernel, image_grid(h, w, n), dim3(NT), 0, s, y, t, (const double*)planes, h, w, base,
+                       tp, ks, kb, dy);
   } else {
     if (vec) COEF(true, false);
     else COEF(false, false);

@@ -9,7 +9,8 @@
 //         elements b * SUM_SPAN + it * 4 * NT + 4 t + (0, 1, 2, 3), in that order, to one fp64
 //         accumulator (elements past n add nothing);
 //       * the 64 lanes of a wave are combined by an xor butterfly (offsets 32, 16, .. 1: every
-//         lane ends with the same sum), the four waves through LDS in wave order by thread 0;
+//         lane ends with the same sum), the four waves through LDS in wave order by thread 0
+//         (reduce.h's block_sum);
 //       * the partial of workgroup b goes to ws[b]; a second launch of ONE workgroup has thread t
 //         add ws[t], ws[t + NT], ... in ascending order and combines the threads the same way.
 //     No atomics, no counter, nothing that depends on which workgroup finishes first: two calls
@@ -25,6 +26,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -35,30 +37,10 @@ constexpr int CLIP_ITERS = 4;
 constexpr long CLIP_SPAN = (long)NT * 4 * CLIP_ITERS;  // 4096 elements per workgroup
 constexpr long MAX_GRID = 0x7FFFFFFFL;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// every thread of the workgroup calls it; the sum is valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v) {
-  __shared__ double wsum[NT / 64];
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-    s = wsum[0];
-#pragma unroll
-    for (int k = 1; k < NT / 64; ++k) s += wsum[k];
-  }
-  return s;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(NT) void grad_sumsq_kernel(const float* __restrict__ g, long n,
                                                         double* __restrict__ part) {
+  __shared__ double red[NT / 64][1];
   const long base = (long)blockIdx.x * SUM_SPAN + 4 * (long)threadIdx.x;
   double acc = 0.0;
   if (VEC && ((long)blockIdx.x + 1) * SUM_SPAN <= n) {
@@ -93,15 +75,16 @@ __global__ __launch_bounds__(NT) void grad_sumsq_kernel(const float* __restrict_
       }
     }
   }
-  const double s = block_sum_f64(acc);
+  const double s = reduce::block_sum<1, NT>({acc}, red);  // valid in thread 0
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(NT) void grad_sumsq_final_kernel(const double* __restrict__ part, long nparts,
                                                               double* __restrict__ out) {
+  __shared__ double red[NT / 64][1];
   double acc = 0.0;
   for (long i = threadIdx.x; i < nparts; i += NT) acc += part[i];
-  const double s = block_sum_f64(acc);
+  const double s = reduce::block_sum<1, NT>({acc}, red);
   if (threadIdx.x == 0) out[0] = s;
 }
 

@@ -27,9 +27,10 @@
 // accumulate with explicit fma(); every other expression is compiled under
 // `#pragma clang fp contract(off)`.
 //
-// Reduction: in-wave shuffles, then LDS across the waves, one (ssim sum, squared-error sum)
-// pair per workgroup into the caller's workspace; metrics_final_kernel folds an image's
-// pairs in a fixed order in fp64.  No atomics: two runs are bitwise equal.
+// Reduction (reduce.h): block_sum, in-wave shuffles, then LDS across the waves, one (ssim sum,
+// squared-error sum) pair per workgroup into the caller's workspace; metrics_final_kernel folds
+// an image's pairs with fold_tree_sum, a fixed order in fp64.  No atomics: two runs are bitwise
+// equal.
 //
 // what == 1 (MSE/PSNR only, any h, w >= 1) takes mse_kernel, a plain strided reduction
 // with the same two-level fold.
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(NT) void mse_kernel(const float* __restrict__ a, co
                                                  double* __restrict__ part) {
   __shared__ double red[NT / 64][2];
   const long img = (long)blockIdx.y * len;
-  double sq = 0.0, zero = 0.0;
+  double sq = 0.0;
   if (VEC) {  // len % 4 == 0 and 16-byte aligned bases
     for (long i = ((long)blockIdx.x * NT + threadIdx.x) * 4; i < len; i += (long)MSE_BLK * NT * 4) {
       const float4 va = *reinterpret_cast<const float4*>(a + img + i);
@@ -77,12 +78,8 @@ __global__ __launch_bounds__(NT) void mse_kernel(const float* __restrict__ a, co
       sq += d * d;
     }
   }
-  block_sum2(zero, sq, red);
-  if (threadIdx.x == 0) {
-    double* d = part + ((long)blockIdx.y * MSE_BLK + blockIdx.x) * 2;
-    d[0] = 0.0;
-    d[1] = sq;
-  }
+  const double s = reduce::block_sum<2, NT>({0.0, sq}, red);  // thread 0: 0, thread 1: the sum
+  if (threadIdx.x < 2) part[((long)blockIdx.y * MSE_BLK + blockIdx.x) * 2 + threadIdx.x] = s;
 }
 
 // one workgroup per image: thread t folds pairs t, t + NT, ... in order, then a fixed tree
@@ -91,21 +88,7 @@ __global__ __launch_bounds__(NT) void metrics_final_kernel(const double* __restr
                                                            double* __restrict__ out) {
   __shared__ double sh[2][NT];
   const int im = blockIdx.x;
-  double ss = 0.0, sq = 0.0;
-  for (long i = threadIdx.x; i < nblk; i += NT) {
-    ss += part[((long)im * nblk + i) * 2];
-    sq += part[((long)im * nblk + i) * 2 + 1];
-  }
-  sh[0][threadIdx.x] = ss;
-  sh[1][threadIdx.x] = sq;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  reduce::fold_tree_sum<2, NT>(part + (long)im * nblk * 2, nblk, sh);
   if (threadIdx.x == 0) {
     if (what & 1) {
       const double mse = sh[1][0] / n_elem;
@@ -145,8 +128,8 @@ extern "C" int cnnitmo_image_metrics(int what, const float* a, const float* b, i
   if (what & 2) {
     const Taps tp = make_taps();
     const double c1 = (0.01 * max_val) * (0.01 * max_val), c2 = (0.03 * max_val) * (0.03 * max_val);
-    const dim3 grid((unsigned)((3L * (w - 2 * R) + TC - 1) / TC), (unsigned)((h - 2 * R + TR - 1) / TR), n);
-    nblk = (long)grid.x * grid.y;
+    const dim3 grid = map_grid(h, w, n);
+    nblk = tiles_of(h, w);
     n_pos = (double)(h - 2 * R) * (w - 2 * R) * 3.0;
     if ((3L * w) % 4 == 0 && aligned16(a) && aligned16(b))
       hipLaunchKernelGGL(ssim_mse_kernel<true>, grid, dim3(NT), 0, s, a, b, h, w, tp, c1, c2, part);

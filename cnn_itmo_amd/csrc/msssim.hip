@@ -97,20 +97,7 @@ __global__ __launch_bounds__(NT) void msssim_final_kernel(const double* __restri
   __shared__ double f[MAX_SCALES][4];
   const int im = blockIdx.x, tid = threadIdx.x;
   for (int k = 0; k < sc.m; ++k) {
-    const double* part = ws + sc.part[k] + (long)im * sc.nblk[k] * 4;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (long i = tid; i < sc.nblk[k]; i += NT)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] += part[i * 4 + j];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[j][tid] = v[j];
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-      if (tid < o)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sh[j][tid] += sh[j][tid + o];
-      __syncthreads();
-    }
+    reduce::fold_tree_sum<4, NT>(ws + sc.part[k] + (long)im * sc.nblk[k] * 4, sc.nblk[k], sh);
     if (tid < 4) f[k][tid] = sh[tid][0];
     __syncthreads();
   }
@@ -167,17 +154,13 @@ __global__ __launch_bounds__(NT) void msssim_grad_kernel(const T* __restrict__ a
     if (gr < h) {
       const long o = img + (long)gr * w3 + (c0 + c);
       const double y = (double)a[o], tg = (double)b[o];
-      const double d = y - tg;
-      double bd = 0.0;
-      if (base == CNNITMO_BASE_MSE) bd = 2.0 * d;
-      else if (base == CNNITMO_BASE_MAE) bd = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
       const double s = (f[0][t] + y * f[1][t]) + tg * f[2][t];
       double v = ksc == 0.0 ? 0.0 : ksc * s;  // (a clamped channel is exactly 0 whatever its planes hold)
       if (gp) {
         const double sy = (gr == h - 1 && (h & 1)) ? 2.0 : 1.0;
         v += (sx * sy) * gp[((long)blockIdx.z * h2 + (gr >> 1)) * 3 * w2 + 3 * (px >> 1) + ch];
       }
-      g[o] = (TO)(v + kb * bd);
+      g[o] = (TO)(v + kb * base_term_slope(base, y - tg));
     }
   }
 }
@@ -268,9 +251,9 @@ extern "C" int cnnitmo_msssim_loss_grad(int base, double alpha, const double* po
   const bool vec = (3L * w) % 4 == 0 && aligned16(y) && aligned16(t);
   for (int k = 0; k < scales; ++k) {  // factors and planes
     const int mh = p.h[k] - 2 * R, mw = p.w[k] - 2 * R;
-    const dim3 grid((unsigned)((3L * mw + TC - 1) / TC), (unsigned)((mh + TR - 1) / TR), n);
+    const dim3 grid = map_grid(p.h[k], p.w[k], n);
     sc.part[k] = p.part[k];
-    sc.nblk[k] = (long)grid.x * grid.y;
+    sc.nblk[k] = tiles_of(p.h[k], p.w[k]);
     sc.npos[k] = (double)mh * mw;
     sc.w[k] = power_factors[k];
     double* planes = grad ? ws + p.planes[k] : nullptr;
@@ -304,7 +287,7 @@ extern "C" int cnnitmo_msssim_loss_grad(int base, double alpha, const double* po
     const double kb = base == CNNITMO_BASE_NONE ? 0.0 : (1.0 - alpha) / (frames * n_elem);
     for (int k = scales - 1; k >= 0; --k) {
       const double ks = -alpha / (frames * (3.0 * sc.npos[k]));
-      const dim3 grid((unsigned)((3L * p.w[k] + TC - 1) / TC), (unsigned)((p.h[k] + TR - 1) / TR), n);
+      const dim3 grid = image_grid(p.h[k], p.w[k], n);
       const double* gp = k + 1 < scales ? ws + p.grad[k + 1] : nullptr;
       if (k == 0)
         hipLaunchKernelGGL((msssim_grad_kernel<float, float>), grid, dim3(NT), 0, s, y, t,

@@ -1,15 +1,23 @@
-// The SSIM tile pass shared by the image metrics (metrics.hip: ssim_mse_kernel), the DSSIM
-// training loss (dssim.hip: dssim_coef_kernel) and the multi-scale loss (msssim.hip:
-// msssim_coef_kernel): one workgroup owns TR x TC positions of the SSIM map of an NHWC RGB image
-// addressed in float columns (see metrics.hip for the layout, the numerics and the reduction).
-// adjoint_pass is the other direction, the full correlation of the coefficient planes with the
-// window, as msssim_grad_kernel runs it per level (dssim_grad_kernel keeps its own copy of that
-// loop, so that it compiles to what it did before the multi-scale loss).  Include this file
-// after `#pragma clang fp contract(off)`: only the filter taps accumulate with (explicit) fma().
+// The one SSIM filter of the image metrics (metrics.hip), the DSSIM training loss (dssim.hip) and
+// the multi-scale loss (msssim.hip), on an NHWC RGB image addressed in float columns (see
+// metrics.hip for the layout and the numerics):
+//   tile_pass     the body of ssim_mse_kernel, dssim_coef_kernel and msssim_coef_kernel: one
+//                 workgroup owns TR x TC positions of the SSIM map, sums the SSIM term and an
+//                 element term over them (reduce.h) and, for a gradient, stores the coefficient
+//                 planes.  Its horizontal pass is row_sums, whatever the input type.
+//   adjoint_pass  the other direction, the body of dssim_grad_kernel and msssim_grad_kernel: the
+//                 full correlation of the coefficient planes with the window.  The kernels differ
+//                 in their epilogues only, which stay with them.
+//   element_term, base_term_slope   the pointwise base term of the losses and its derivative
+//   map_grid, image_grid, tiles_of  the launch grids of the two passes and the tiles per image
+// The kernels that share a body are held to identical results and measured time, not to identical
+// device code (the multi-scale section).  Include this file after
+// `#pragma clang fp contract(off)`: only the filter taps accumulate with (explicit) fma().
 #pragma once
 #include <math.h>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace ssim_tile {
 
@@ -38,39 +46,21 @@ static inline Taps make_taps() {
   return tp;
 }
 
-// tiles of the SSIM map of an h x w image (h, w >= NTAP)
+// the launch grid of the TR x TC tiles of an n x h x w image's float columns (adjoint_pass's grid)
+static inline dim3 image_grid(int h, int w, int n) {
+  return dim3((unsigned)((3L * w + TC - 1) / TC), (unsigned)((h + TR - 1) / TR), (unsigned)n);
+}
+
+// the launch grid of the tiles of its SSIM map (tile_pass's grid; h, w >= NTAP)
+static inline dim3 map_grid(int h, int w, int n) { return image_grid(h - 2 * R, w - 2 * R, n); }
+
+// tiles of the SSIM map of an h x w image: the partials per image that the workspaces are sized by
 static inline long tiles_of(int h, int w) {
-  const long ty = (h - 2 * R + TR - 1) / TR, tx = (3L * (w - 2 * R) + TC - 1) / TC;
-  return ty * tx;
+  const dim3 g = map_grid(h, w, 1);
+  return (long)g.x * g.y;
 }
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum of (v0, v1) over the workgroup -> thread 0
-__device__ __forceinline__ void block_sum2(double& v0, double& v1, double (*sh)[2]) {
-  v0 = wave_sum_f64(v0);
-  v1 = wave_sum_f64(v1);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-    sh[wave][0] = v0;
-    sh[wave][1] = v1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    v0 = sh[0][0];
-    v1 = sh[0][1];
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
-      v0 += sh[i][0];
-      v1 += sh[i][1];
-    }
-  }
-}
 
 // What a tile sums beside the SSIM term, per element d = a - b, and whether it stores the
 // gradient's coefficient planes (dssim.hip)
@@ -80,6 +70,53 @@ template <int MODE>
 __device__ __forceinline__ double element_term(int base, double d) {
   if constexpr (MODE == SQUARED_ERROR) return d * d;
   return base == CNNITMO_BASE_MSE ? d * d : (base == CNNITMO_BASE_MAE ? fabs(d) : 0.0);
+}
+
+// the base term's derivative in d: 2 d ('mse'), sign(d) with sign(0) = 0 ('mae'), 0 (none)
+__device__ __forceinline__ double base_term_slope(int base, double d) {
+  if (base == CNNITMO_BASE_MSE) return 2.0 * d;
+  if (base == CNNITMO_BASE_MAE) return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+  return 0.0;
+}
+
+// (r, cb) of horizontal-pass item i < IR * (TC / G): staged row r; the thread's outputs are the
+// float columns cb + 3 t, t < G (one channel of G neighbouring pixels), from inputs cb + 3 m, m < GW
+__device__ __forceinline__ void row_item(int i, int& r, int& cb) {
+  const int gi = i % (TC / G);
+  r = i / (TC / G);
+  cb = (gi / 3) * (3 * G) + gi % 3;
+}
+
+// the horizontal pass of one item: the row sums of the five maps x, y, xx, yy, xy
+struct RowSums {
+  double v[5][G];
+};
+
+template <typename T>
+__device__ __forceinline__ RowSums row_sums(const T (&sa)[IR][ICP], const T (&sb)[IR][ICP], const Taps& tp, int r,
+                                            int cb) {
+  RowSums acc;
+#pragma unroll
+  for (int k = 0; k < 5; ++k)
+#pragma unroll
+    for (int t = 0; t < G; ++t) acc.v[k][t] = 0.0;
+#pragma unroll
+  for (int m = 0; m < GW; ++m) {
+    const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
+    const double xx = x * x, yy = y * y, xy = x * y;
+#pragma unroll
+    for (int t = 0; t < G; ++t) {
+      if (m - t >= 0 && m - t < NTAP) {
+        const double g = tp.g[m - t];
+        acc.v[0][t] = fma(g, x, acc.v[0][t]);
+        acc.v[1][t] = fma(g, y, acc.v[1][t]);
+        acc.v[2][t] = fma(g, xx, acc.v[2][t]);
+        acc.v[3][t] = fma(g, yy, acc.v[3][t]);
+        acc.v[4][t] = fma(g, xy, acc.v[4][t]);
+      }
+    }
+  }
+  return acc;
 }
 
 // The body of a tile kernel; grid (tiles_x, tiles_y, n), NT threads.
@@ -104,7 +141,8 @@ __device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __re
   __shared__ T sa[IR][ICP];
   __shared__ T sb[IR][ICP];
   __shared__ double hs[ALIAS ? 3 : 5][IR][TC];
-  __shared__ double red[NT / 64][PER_CHANNEL ? 4 : 2];
+  constexpr int NP = PER_CHANNEL ? 4 : 2;  // partial sums per tile
+  __shared__ double red[NT / 64][NP];
 
   const int tid = threadIdx.x;
   const int w3 = 3 * w;
@@ -152,7 +190,7 @@ __device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __re
   }
   __syncthreads();
 
-  // horizontal pass: thread = (row, base column cb); outputs cb + 3t, t < G, from inputs cb + 3m, m < GW
+  // horizontal pass (row_sums): the five row sums of every item go to hs; ALIAS has room for three
   double (*hs3)[TC] = nullptr, (*hs4)[TC] = nullptr;  // ALIAS: the row sums of yy and xy
   if constexpr (ALIAS) {
     double keep[HI][2][G];  // yy and xy stay in registers until every thread has read the windows
@@ -160,35 +198,15 @@ __device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __re
     for (int it = 0; it < HI; ++it) {
       const int i = tid + it * NT;
       if (i < IR * (TC / G)) {
-        const int r = i / (TC / G), gi = i % (TC / G);
-        const int cb = (gi / 3) * (3 * G) + gi % 3;
-        double acc[5][G];  // (the else branch's sums: a shared helper changed the fp32 kernels' schedule)
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-#pragma unroll
-          for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
-#pragma unroll
-        for (int m = 0; m < GW; ++m) {
-          const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
-          const double xx = x * x, yy = y * y, xy = x * y;
-#pragma unroll
-          for (int t = 0; t < G; ++t) {
-            if (m - t >= 0 && m - t < NTAP) {
-              const double g = tp.g[m - t];
-              acc[0][t] = fma(g, x, acc[0][t]);
-              acc[1][t] = fma(g, y, acc[1][t]);
-              acc[2][t] = fma(g, xx, acc[2][t]);
-              acc[3][t] = fma(g, yy, acc[3][t]);
-              acc[4][t] = fma(g, xy, acc[4][t]);
-            }
-          }
-        }
+        int r, cb;
+        row_item(i, r, cb);
+        const RowSums acc = row_sums(sa, sb, tp, r, cb);
 #pragma unroll
         for (int t = 0; t < G; ++t) {
 #pragma unroll
-          for (int k = 0; k < 3; ++k) hs[k][r][cb + 3 * t] = acc[k][t];
-          keep[it][0][t] = acc[3][t];
-          keep[it][1][t] = acc[4][t];
+          for (int k = 0; k < 3; ++k) hs[k][r][cb + 3 * t] = acc.v[k][t];
+          keep[it][0][t] = acc.v[3][t];
+          keep[it][1][t] = acc.v[4][t];
         }
       }
     }
@@ -199,8 +217,8 @@ __device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __re
     for (int it = 0; it < HI; ++it) {
       const int i = tid + it * NT;
       if (i < IR * (TC / G)) {
-        const int r = i / (TC / G), gi = i % (TC / G);
-        const int cb = (gi / 3) * (3 * G) + gi % 3;
+        int r, cb;
+        row_item(i, r, cb);
 #pragma unroll
         for (int t = 0; t < G; ++t) {
           hs3[r][cb + 3 * t] = keep[it][0][t];
@@ -210,33 +228,13 @@ __device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __re
     }
   } else {
     for (int i = tid; i < IR * (TC / G); i += NT) {
-      const int r = i / (TC / G), gi = i % (TC / G);
-      const int cb = (gi / 3) * (3 * G) + gi % 3;
-      double acc[5][G];
+      int r, cb;
+      row_item(i, r, cb);
+      const RowSums acc = row_sums(sa, sb, tp, r, cb);
 #pragma unroll
       for (int k = 0; k < 5; ++k)
 #pragma unroll
-        for (int t = 0; t < G; ++t) acc[k][t] = 0.0;
-#pragma unroll
-      for (int m = 0; m < GW; ++m) {
-        const double x = (double)sa[r][cb + 3 * m], y = (double)sb[r][cb + 3 * m];
-        const double xx = x * x, yy = y * y, xy = x * y;
-#pragma unroll
-        for (int t = 0; t < G; ++t) {
-          if (m - t >= 0 && m - t < NTAP) {
-            const double g = tp.g[m - t];
-            acc[0][t] = fma(g, x, acc[0][t]);
-            acc[1][t] = fma(g, y, acc[1][t]);
-            acc[2][t] = fma(g, xx, acc[2][t]);
-            acc[3][t] = fma(g, yy, acc[3][t]);
-            acc[4][t] = fma(g, xy, acc[4][t]);
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 5; ++k)
-#pragma unroll
-        for (int t = 0; t < G; ++t) hs[k][r][cb + 3 * t] = acc[k][t];
+        for (int t = 0; t < G; ++t) hs[k][r][cb + 3 * t] = acc.v[k][t];
     }
   }
   __syncthreads();
@@ -309,30 +307,19 @@ __device__ __forceinline__ void tile_pass(const T* __restrict__ a, const T* __re
     }
   }
 
+  // the tile's NP sums, one thread each (reduce.h); PER_CHANNEL: the vertical pass gave this thread
+  // column tid % TC of a tile that starts at a red column
+  double v[NP];
   if constexpr (PER_CHANNEL) {
-    // the vertical pass gave this thread column tid % TC of a tile that starts at a red column
     const int ch = (tid % TC) % 3;
-    double v[4] = {ch == 0 ? ss : 0.0, ch == 1 ? ss : 0.0, ch == 2 ? ss : 0.0, sq};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[k] = wave_sum_f64(v[k]);
-      if ((tid & 63) == 0) red[tid >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (tid < 4) {
-      double s = red[0][tid];
-      for (int i = 1; i < NT / 64; ++i) s += red[i][tid];
-      const long nblk = (long)gridDim.x * gridDim.y;
-      part[((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + tid] = s;
-    }
+    v[0] = ch == 0 ? ss : 0.0, v[1] = ch == 1 ? ss : 0.0, v[2] = ch == 2 ? ss : 0.0, v[3] = sq;
   } else {
-    block_sum2(ss, sq, red);
-    if (tid == 0) {
-      const long nblk = (long)gridDim.x * gridDim.y;
-      double* d = part + ((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-      d[0] = ss;
-      d[1] = sq;
-    }
+    v[0] = ss, v[1] = sq;
+  }
+  const double s = reduce::block_sum<NP, NT>(v, red);
+  if (tid < NP) {
+    const long nblk = (long)gridDim.x * gridDim.y;
+    part[((long)blockIdx.z * nblk + (long)blockIdx.y * gridDim.x + blockIdx.x) * NP + tid] = s;
   }
 }
 
@@ -369,8 +356,8 @@ __device__ __forceinline__ void adjoint_pass(const double* __restrict__ planes, 
     // horizontal pass: staged column cb + 3m holds map column c0 + cb - 30 + 3m; output column
     // cb + 3t takes it with tap g[10 - (m - t)]
     for (int i = tid; i < IR * (TC / G); i += NT) {
-      const int r = i / (TC / G), gi = i % (TC / G);
-      const int cb = (gi / 3) * (3 * G) + gi % 3;
+      int r, cb;
+      row_item(i, r, cb);
       double acc[G];
 #pragma unroll
       for (int t = 0; t < G; ++t) acc[t] = 0.0;

@@ -25,6 +25,7 @@
 // HBM-bound: 12 B read + 12 B (fp32) / 3 B (u8) written per pixel per map; the
 // statistics pass reads 12 B (fp32) or 3 B (u8) per pixel.
 #include "common.h"
+#include "reduce.h"
 #include "tonemap_px.h"  // Lum, lum, REALMIN, im2uint8, lum_of
 
 // no FMA contraction: the products and sums round like MATLAB's (and numpy's) doubles
@@ -63,16 +64,7 @@ __global__ __launch_bounds__(TB) void stats_partial_kernel(int mode, const void*
     z += Y == 0.0 ? 1.0 : 0.0;
   }
   __shared__ double sh[2][TB];
-  sh[0][threadIdx.x] = s;
-  sh[1][threadIdx.x] = z;
-  __syncthreads();
-  for (int o = TB / 2; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  reduce::tree_sum<2, TB>({s, z}, sh);
   if (threadIdx.x == 0) {
     double* d = part + ((long)im * BLK_PER_IMG + blockIdx.x) * 2;
     d[0] = sh[0][0];
@@ -80,23 +72,15 @@ __global__ __launch_bounds__(TB) void stats_partial_kernel(int mode, const void*
   }
 }
 
-// One block per image folds its BLK_PER_IMG block sums with the same fixed tree as above.  (A sequential
+// One block per image folds its BLK_PER_IMG block sums with the same fixed tree (reduce.h) as above.  (A sequential
 // fold of near-equal block sums rounds the same way at every step: 4e-15 of the sum for a constant image
 // of 256 x 256, where the tree is exact.)
 __global__ __launch_bounds__(BLK_PER_IMG) void stats_final_kernel(const double* __restrict__ part,
                                                                   double* __restrict__ stats) {
   const int im = blockIdx.x;
   __shared__ double sh[2][BLK_PER_IMG];
-  sh[0][threadIdx.x] = part[((long)im * BLK_PER_IMG + threadIdx.x) * 2];
-  sh[1][threadIdx.x] = part[((long)im * BLK_PER_IMG + threadIdx.x) * 2 + 1];
-  __syncthreads();
-  for (int o = BLK_PER_IMG / 2; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  const double* p = part + ((long)im * BLK_PER_IMG + threadIdx.x) * 2;
+  reduce::tree_sum<2, BLK_PER_IMG>({p[0], p[1]}, sh);
   if (threadIdx.x == 0) {
     stats[2 * im] = sh[0][0];
     stats[2 * im + 1] = sh[1][0];
