@@ -6,6 +6,8 @@ With CNNITMO_HALO=0 this runs the existing checks, imported and not copied, at t
 
   * test_gpu_ops.conv3x3_case (test_conv3x3_fwd_dgrad_wgrad's body) on kernel_cases.CONV3X3_HALO0;
   * test_gpu_ops.affine_epilogue_case (test_conv_affine_inference_epilogue's body) on AFFINE_HALO0;
+  * test_gpu_exact.conv3x3_exact and affine_exact (the bit-for-bit cases on integer operands,
+    tests/exact_cases.py) on the same two lists, both regimes;
   * test_gpu_model.test_unet_train_step_parity, both dtypes.
 
 Every 3x3 conv launch goes through ops.call: its kernel name is asked first and must start with
@@ -31,6 +33,8 @@ def main():
     from cnn_itmo_amd import _lib as L
     from cnn_itmo_amd import ops
     from tests import kernel_cases as KC
+    from tests import exact_cases as E
+    from tests import test_gpu_exact as X
     from tests import test_gpu_model as M
     from tests import test_gpu_ops as T
 
@@ -61,6 +65,15 @@ def main():
     for (dt, h, w, cin, cout), name in KC.AFFINE_HALO0.items():
         T.affine_epilogue_case(dt, h, w, cin, cout, name)
         print(f"affine epilogue {cin}->{cout} {h}x{w} {dt}: {name}: ok", flush=True)
+    for regime in E.REGIMES:
+        for (cin, cout, h, w), names in KC.CONV3X3_HALO0.items():
+            for dt in ("f32", "bf16"):
+                X.conv3x3_exact(dt, cin, cout, h, w, regime, names[dt])
+                print(f"exact {regime} conv3x3 {cin}->{cout} {h}x{w} {dt}: fwd {names[dt][0]}, dgrad {names[dt][1]}: "
+                      "every bit", flush=True)
+        for (dt, h, w, cin, cout), name in KC.AFFINE_HALO0.items():
+            X.affine_exact(dt, h, w, cin, cout, regime, name)
+            print(f"exact {regime} affine epilogue {cin}->{cout} {h}x{w} {dt}: {name}: every bit", flush=True)
     cases = dict(seen)
     for dtype in ("float32", "bfloat16"):
         M.test_unet_train_step_parity(dtype)

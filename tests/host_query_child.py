@@ -4,6 +4,8 @@
     python tests/host_query_child.py launch    wgrad launches with channel counts below 32
     python tests/host_query_child.py names     kernel names as JSON (tests/kernel_cases.py),
                                                under whatever CNNITMO_HALO the parent set
+    python tests/host_query_child.py exact_names   the same for the bit-exact cases
+                                               (tests/exact_cases.py: launched)
 
 Each call is printed before it is made (unbuffered), so that after a signal the parent can
 report the last line as the call that killed the process.  The library is loaded through
@@ -164,5 +166,15 @@ def names():
     say(json.dumps(out))
 
 
+def exact_names():
+    sys.path.insert(0, ROOT)
+    from tests import exact_cases as E
+    from tests import kernel_cases as KC
+    _, lib = load_lib()
+    q = lambda name, *a: getattr(lib, name)(*a)  # noqa: E731
+    halo0 = os.environ.get("CNNITMO_HALO") == "0"
+    say(json.dumps({"tested": KC.tested(q, halo0), "launched": E.launched(q, halo0)}))
+
+
 if __name__ == "__main__":
-    {"sweep": sweep, "launch": launch, "names": names}[sys.argv[1]]()
+    {"sweep": sweep, "launch": launch, "names": names, "exact_names": exact_names}[sys.argv[1]]()

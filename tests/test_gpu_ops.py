@@ -607,7 +607,8 @@ def test_conv3x3_fwd_cat_dec9(H, W):
 def test_conv3x3_without_halo_kernel():
     """CNNITMO_HALO=0, the supported switch for A/B runs of the halo kernel and the path of every
     shape halo_plan refuses: the 9-tap implicit GEMMs (igemm_fwd_kernel, igemm_fwd2_kernel) at this
-    file's bounds for the forward, input gradient and inference epilogue, and a whole training step
+    file's bounds for the forward, input gradient and inference epilogue, the same cases bit for bit
+    on integer operands (tests/exact_cases.py, both regimes), and a whole training step
     at test_unet_train_step_parity's.  The variable is read once per process: one fresh child
     (tests/halo0_child.py), which stops at its first failure."""
     import subprocess
@@ -623,3 +624,8 @@ def test_conv3x3_without_halo_kernel():
     assert "halo0 child ok" in r.stdout
     launched = [ln for ln in r.stdout.splitlines() if ln.startswith("conv3x3 ")]
     assert len(launched) == 2 * len(KC.CONV3X3_HALO0) and all("fwd igemm_" in ln and "dgrad igemm_" in ln for ln in launched)
+    # the same lists again on exactly representable integers, bit for bit (tests/test_gpu_exact.py's bodies)
+    for regime in ("small", "wide"):
+        exact = [ln for ln in r.stdout.splitlines() if ln.startswith(f"exact {regime} ") and ln.endswith(": every bit")]
+        assert sum(" conv3x3 " in ln and "fwd igemm_" in ln and "dgrad igemm_" in ln for ln in exact) == 2 * len(KC.CONV3X3_HALO0)
+        assert sum(" affine epilogue " in ln and ": igemm_" in ln for ln in exact) == len(KC.AFFINE_HALO0)
