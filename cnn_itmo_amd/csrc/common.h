@@ -81,6 +81,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 // Host-side error plumbing.
 void cnnitmo_set_error(const char* fmt, ...);
 int cnnitmo_check_launch(const char* what);
+// Compute units of the current device (asked once); 256 when there is no device to ask.
+int cnnitmo_cu_count();
 
 #define CNN_REQUIRE(cond, ...)                \
   do {                                        \

@@ -43,7 +43,6 @@
 // g (as cnnitmo_bn_bwd_apply computes it) plus sums of dz by pixel parity; the
 // other columns are stored as g.
 #include <cstdio>
-#include <type_traits>
 
 #include "dma.h"
 #include "igemm_common.h"
@@ -690,7 +689,7 @@ __global__ __launch_bounds__(NT) void halo_conv_kernel(const HaloArgs h) {
       lds8(par + 2 * BN + cl, ce);
       // ALLF: the pair's columns at the wave's first pixel, in dz (a fused block) or in the plain
       // gradient's view (a block below c0, whose r reads as 0: the ReLU test then compares with -1)
-      // (the resident-weight and routed kernels take c0 = 0 only: launch_cfg)
+      // (the resident-weight and routed kernels take c0 = 0 only: halo_plan)
       const bool bfz = !ALLF || RES || POOL || n0 >= c0;
       const __amdgpu_buffer_rsrc_t zs =
           dma::brsrc(!ALLF ? (const void*)Z
@@ -996,22 +995,12 @@ __global__ __launch_bounds__(NT) void halo_conv_kernel(const HaloArgs h) {
   }
 }
 
+// One launch, whole: the grid and every template argument of the instantiation.
 struct HaloPlan {
+  int grid;  // workgroups: one per CU
   int bn, epi, th;
-  bool res;
+  bool f32, res, pool, alt;  // (halo_conv_kernel's TE, RES, POOL and ALT)
 };
-
-int halo_ncu() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount;
-    if (ncu < 8) ncu = 256;
-  }
-  return ncu;
-}
 
 // conv3x3 stride 1 'same' (forward or input-gradient), 64-byte chunks (32 bf16 / 16 fp32
 // channels); fp32: one source (forward with BN sums, plain and fused input gradients)
@@ -1039,6 +1028,8 @@ bool halo_plan(const FwdArgs& a, HaloPlan& pl, bool f32 = false) {
   if (a.pool_out && a.bnb_out && (a.bnb_c0 != 0 || a.bnb_c1 != a.N || a.pool_ld != a.N || a.bnb_par)) return false;
   // pooled forward: BN sums (training, BN folded: r stored) or the affine (inference), not both
   if (a.pool_out && (a.flags & CNNITMO_STATS) && (a.flags & CNNITMO_AFFINE)) return false;
+  pl.f32 = f32;
+  pl.pool = a.pool_out != nullptr;
   pl.bn = a.N % 64 == 0 ? 64 : (a.N % 32 == 0 ? 32 : 0);
   // the routed-pool dgrad (EPI 2 + POOL): 32-column blocks, whose epilogue keeps the pooled
   // gradient and indices in registers without spilling (64-column blocks measured 0.3 %
@@ -1046,70 +1037,68 @@ bool halo_plan(const FwdArgs& a, HaloPlan& pl, bool f32 = false) {
   // dgrads keep 64 columns: 32-column blocks, whose r loads can go out early, measured 3 %
   // slower for all of them and 1 % for those up to 64 columns (r05e_ab_bnb_bn32.txt,
   // r05h_ab_bnb_bn32_64.txt)
-  if (a.pool_out && a.bnb_out && a.N % 32 == 0) pl.bn = 32;
-  if (!pl.bn || a.N / pl.bn > halo_ncu() / 8) return false;
+  if (pl.pool && a.bnb_out && a.N % 32 == 0) pl.bn = 32;
+  // one workgroup per CU, each XCD's share dealt into streams (a device of fewer than 8 CUs
+  // is planned as 256)
+  pl.grid = cnnitmo_cu_count() < 8 ? 256 : cnnitmo_cu_count();
+  if (!pl.bn || a.N / pl.bn > pl.grid / 8) return false;
+  pl.res = a.cin <= (f32 ? 16 : 32) * RCH;
+  pl.th = 16;
   if (a.bnb_out) {  // fused BN backward (input gradient)
     if (a.bnb_c0 % 8 || a.bnb_c1 % 8 || a.bnb_c0 < 0 || a.bnb_c1 > a.N || a.bnb_c0 >= a.bnb_c1 ||
         a.bnb_r_ld % 8 || a.bnb_r_off % 8)
       return false;
     pl.epi = 2;
+    // ALLF: every column fused (the routed pooled gradient always), or (bf16, streamed weights)
+    // every block either fused or plain
+    pl.alt = a.bnb_c1 == a.N && (a.bnb_c0 == 0 || (!f32 && !pl.res && a.bnb_c0 % pl.bn == 0));
   } else if (a.yhat) {  // the forward with the sigmoid head (one 64-column block: all channels)
     if (a.N != 64 || pl.bn != 64 || a.a2 || a.pool_out || a.stats || a.border || (a.flags & CNNITMO_STATS) ||
         !a.head_w || !a.head_b)
       return false;
     pl.epi = 3;
+    pl.alt = false;
   } else {
     pl.epi = (a.flags || a.bias || a.border || a.stats) ? 1 : 0;
-    if (a.a2 && pl.epi != 1) return false;  // two sources: the forward-epilogue kernels only
+    if ((a.a2 || pl.pool) && pl.epi != 1) return false;  // two sources, pooling: the forward-epilogue kernels only
+    pl.alt = pl.epi == 1 && !(a.flags & CNNITMO_STATS);  // NOSUM (inference): the kernels without BN sums
   }
-  pl.res = a.cin <= (f32 ? 16 : 32) * RCH;
-  pl.th = 16;
   return true;
 }
 
-template <typename T, int BN, int EPI>
-void launch_cfg(const HaloArgs& h, bool res, int grid, hipStream_t s) {
-  if constexpr (EPI == 2) {
-    if (h.f.pool_out) {  // the routed pooled gradient (cnnitmo_conv3x3_dgrad_bn_pooled; 32-column blocks,
-                         // every column fused: halo_plan)
-      if constexpr (BN == 32) {
-        if (res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true, true, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-        else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false, true, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-      }
-      return;
-    }
-    // ALLF: every column fused, or (bf16) every block either fused or plain
-    const bool allf = h.f.bnb_c1 == h.f.N &&
-                      (h.f.bnb_c0 == 0 || (std::is_same<T, bf16>::value && !res && h.f.bnb_c0 % BN == 0));
-    if (allf) {
-      if (res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true, false, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-      else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false, false, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-      return;
-    }
-  }
-  if constexpr (EPI == 1) {
-    const bool nst = !(h.f.flags & CNNITMO_STATS);  // inference: the kernels without BN sums
-    if (h.f.pool_out) {
-      if (nst) {
-        if (res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true, true, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-        else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false, true, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-      } else {
-        if (res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true, true>), dim3(grid), dim3(NT), 0, s, h);
-        else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false, true>), dim3(grid), dim3(NT), 0, s, h);
-      }
-      return;
-    }
-    if (nst) {
-      if (res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true, false, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-      else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false, false, 16, true>), dim3(grid), dim3(NT), 0, s, h);
-      return;
-    }
-  }
-  if (res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true>), dim3(grid), dim3(NT), 0, s, h);
-  else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false>), dim3(grid), dim3(NT), 0, s, h);
+template <typename T, int BN, int EPI, bool POOL, bool ALT>
+void launch_inst(const HaloArgs& h, const HaloPlan& pl, hipStream_t s) {
+  if (pl.res) hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, true, POOL, 16, ALT>), dim3(pl.grid), dim3(NT), 0, s, h);
+  else hipLaunchKernelGGL((halo_conv_kernel<T, BN, EPI, false, POOL, 16, ALT>), dim3(pl.grid), dim3(NT), 0, s, h);
 }
 
-int halo_streams(const FwdArgs& a, const HaloPlan& pl) { return halo_ncu() / (a.N / pl.bn); }
+constexpr int halo_key(bool f32, int bn, int epi, bool pool, bool alt) {
+  return (((f32 * 2 + (bn == 64)) * 4 + epi) * 2 + pool) * 2 + alt;
+}
+
+// Every instantiation there is (T, BN, EPI, POOL, ALT; each with and without RES).
+#define HALO_EPI1(X, T, BN) X(T, BN, 1, true, true) X(T, BN, 1, true, false) X(T, BN, 1, false, true) X(T, BN, 1, false, false)
+#define HALO_EPI2(X, T) \
+  X(T, 64, 2, false, true) X(T, 64, 2, false, false) X(T, 32, 2, true, true) X(T, 32, 2, false, true) X(T, 32, 2, false, false)
+#define HALO_INSTANCES(X)                                                       \
+  X(float, 64, 3, false, false) HALO_EPI1(X, float, 64) HALO_EPI1(X, float, 32) \
+  HALO_EPI2(X, float) X(float, 64, 0, false, false) X(float, 32, 0, false, false) \
+  HALO_EPI2(X, bf16) X(bf16, 64, 3, false, false) HALO_EPI1(X, bf16, 64) HALO_EPI1(X, bf16, 32) \
+  X(bf16, 64, 0, false, false) X(bf16, 32, 0, false, false)
+
+bool launch_plan(const HaloArgs& h, const HaloPlan& pl, hipStream_t s) {
+  switch (halo_key(pl.f32, pl.bn, pl.epi, pl.pool, pl.alt)) {
+#define HALO_CASE(T, BN, EPI, POOL, ALT)                      \
+  case halo_key(sizeof(T) == 4, BN, EPI, POOL, ALT):          \
+    launch_inst<T, BN, EPI, POOL, ALT>(h, pl, s);             \
+    return true;
+    HALO_INSTANCES(HALO_CASE)
+#undef HALO_CASE
+  }
+  return false;
+}
+
+int halo_streams(const FwdArgs& a, const HaloPlan& pl) { return pl.grid / (a.N / pl.bn); }
 
 }  // namespace
 
@@ -1132,29 +1121,10 @@ int launch_halo(FwdArgs a, hipStream_t s, const char* what, bool f32) {
   CNN_REQUIRE(h.streams >= 1, "%s: %d column blocks exceed the workgroups", what, h.nblocks);
   CNN_REQUIRE(h.tiles * h.nchunks < (1L << 31), "%s: too many tiles", what);
   CNN_REQUIRE(!(a.flags & CNNITMO_STATS) || a.stats, "%s: STATS without buffer", what);
-  const int grid = halo_ncu();
-  if (f32 && pl.epi == 3) {
-    launch_cfg<float, 64, 3>(h, pl.res, grid, s);
-  } else if (f32 && pl.epi == 1) {
-    if (pl.bn == 64) launch_cfg<float, 64, 1>(h, pl.res, grid, s);
-    else launch_cfg<float, 32, 1>(h, pl.res, grid, s);
-  } else if (f32 && pl.epi == 2) {
-    if (pl.bn == 64) launch_cfg<float, 64, 2>(h, pl.res, grid, s);
-    else launch_cfg<float, 32, 2>(h, pl.res, grid, s);
-  } else if (f32) {
-    if (pl.bn == 64) launch_cfg<float, 64, 0>(h, pl.res, grid, s);
-    else launch_cfg<float, 32, 0>(h, pl.res, grid, s);
-  } else if (pl.epi == 2) {
-    if (pl.bn == 64) launch_cfg<bf16, 64, 2>(h, pl.res, grid, s);
-    else launch_cfg<bf16, 32, 2>(h, pl.res, grid, s);
-  } else if (pl.epi == 3) {
-    launch_cfg<bf16, 64, 3>(h, pl.res, grid, s);
-  } else if (pl.epi == 1) {
-    if (pl.bn == 64) launch_cfg<bf16, 64, 1>(h, pl.res, grid, s);
-    else launch_cfg<bf16, 32, 1>(h, pl.res, grid, s);
-  } else {
-    if (pl.bn == 64) launch_cfg<bf16, 64, 0>(h, pl.res, grid, s);
-    else launch_cfg<bf16, 32, 0>(h, pl.res, grid, s);
+  if (!launch_plan(h, pl, s)) {
+    cnnitmo_set_error("%s: no halo kernel for %d-column blocks, epilogue %d%s%s", what, pl.bn, pl.epi,
+                      pl.pool ? ", pooled" : "", pl.alt ? ", alt" : "");
+    return CNNITMO_EUNSUPPORTED;
   }
   return cnnitmo_check_launch(what);
 }
@@ -1164,7 +1134,7 @@ const char* halo_name(const FwdArgs& a, bool f32) {
   if (!halo_plan(a, pl, f32)) return "";
   static thread_local char buf[64];
   snprintf(buf, sizeof(buf), "halo_conv_kernel<%s%d,%d%s%s>", f32 ? "f32," : "", pl.bn, pl.epi, pl.res ? ",wres" : "",
-           a.pool_out ? (pl.epi == 2 ? ",route" : ",pool") : "");
+           pl.pool ? (pl.epi == 2 ? ",route" : ",pool") : "");
   return buf;
 }
 

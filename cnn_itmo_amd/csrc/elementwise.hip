@@ -30,6 +30,16 @@ int cnnitmo_check_launch(const char* what) {
   }
   return CNNITMO_OK;
 }
+int cnnitmo_cu_count() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      return 256;
+    return v;
+  }();
+  return n;
+}
 extern "C" const char* cnnitmo_last_error(void) { return g_err; }
 // 2: CNNITMO_CONSUMER_ROWS 16 -> 64 (query it with cnnitmo_consumer_rows) and cnnitmo_bn_apply's
 //    scale / shift must be 16-byte aligned

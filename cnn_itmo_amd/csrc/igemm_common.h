@@ -120,14 +120,26 @@ template <> struct Mma<float> {
 };
 
 
+// v1 (register-staged) forward family, igemm_fwd.hip
+template <typename T>
+int launch_fwd(FwdArgs a, hipStream_t s, const char* what);
+bool fwd_sizes_ok(const FwdArgs& a, int ve);  // dense views pass launch_fwd's requirements
+int fwd_stat_rows(long m, int N);
+const char* fwd_name(int N, bool bf16);
+
 // v2 (direct-to-LDS pipelined) forward family, igemm_fwd2.hip
+enum Fwd2Kind { FWD2_PERS256, FWD2_T256, FWD2_T128, FWD2_STAGED };
+struct Fwd2Plan {
+  Fwd2Kind kind;  // persistent 256 x 256, 256 x 256, 128 x 128, or the staged 256 x bn tiles
+  int bm, bn;
+};
+Fwd2Plan fwd2_plan(const FwdArgs& a, bool bf16);
 template <typename T>
 int launch_fwd2(FwdArgs a, hipStream_t s, const char* what);
+bool fwd2_sizes_ok(const FwdArgs& a, int ve);  // dense views pass launch_fwd2's requirements
 int fwd2_stat_rows(long m);
+const char* fwd2_name(const FwdArgs& a, bool bf16);
 bool fwd2_handles(int N);  // v2 is the faster kernel for this column count
-int fwd2_bm(const FwdArgs& a, bool bf16);  // row tile of the v2 launch (128 or 256)
-bool fwd2_t256(const FwdArgs& a, bool bf16);  // 256 x 256 tiles (bf16 tconv input gradient)
-bool fwd2_pers(const FwdArgs& a, bool bf16);  // ... in the persistent kernel
 // the bf16 Conv2DTranspose forward in training, persistent (igemm_fwd2.hip)
 bool tfwd2p_handles(const FwdArgs& a, bool bf16);
 long tfwd2p_stat_rows(const FwdArgs& a);

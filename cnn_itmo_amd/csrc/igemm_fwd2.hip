@@ -703,36 +703,39 @@ void launch_st(const FwdArgs& a, hipStream_t s, dim3 grid) {
 }  // namespace
 
 int fwd2_stat_rows(long m) { return (int)((m + 255) / 256); }
-
-// Row tile of the v2 launch: 128 x 128 tiles with a 2-deep ring (64-68 KB, two
-// workgroups per CU: one workgroup's prologue and LDS-staged epilogue overlap the
-// other's MFMAs) for the bf16 Conv2DTranspose input gradient (up6/up7 0.87/1.93 ->
-// 0.83/1.81 ms) and for every fp32 launch with N % 128 == 0 (inference dec6-dec8
-// 15.4-15.8 -> 15.0-15.3 ms); launches with BN partial sums keep 256-row tiles (the
-// sums rows are per 256 rows).
-int fwd2_bm(const FwdArgs& a, bool bf16) {
-  if (a.N % 128 || a.stats) return 256;
-  return (!bf16 || (a.ntaps == 4 && a.scale == 2)) ? 128 : 256;
-}
 bool fwd2_handles(int N) { return N != 32; }
 
-// bf16 Conv2DTranspose input gradient (K = 1024 / 2048): 256 x 256 tiles (8 waves of
-// 128 x 64, 2-deep 128 KB ring, one workgroup per CU) move half the LDS-DMA bytes per
-// MFMA of the 128 x 128 tiles: up6 / up7 0.83 / 1.80 -> 0.70 / 1.66 ms
-// (profiles/r03z_ab_fwd2_256.txt)
-bool fwd2_t256(const FwdArgs& a, bool bf16) {
-  return bf16 && a.ntaps == 4 && a.scale == 2 && a.N % 256 == 0 && !a.stats;
+Fwd2Plan fwd2_plan(const FwdArgs& a, bool bf16) {
+  const bool tdgrad = a.ntaps == 4 && a.scale == 2;  // the Conv2DTranspose input gradient
+  // bf16 Conv2DTranspose input gradient (K = 1024 / 2048): 256 x 256 tiles (8 waves of
+  // 128 x 64, 2-deep 128 KB ring, one workgroup per CU) move half the LDS-DMA bytes per
+  // MFMA of the 128 x 128 tiles: up6 / up7 0.83 / 1.80 -> 0.70 / 1.66 ms
+  // (profiles/r03z_ab_fwd2_256.txt)
+  if (bf16 && tdgrad && a.N % 256 == 0 && !a.stats) {
+    // ... as the persistent kernel (igemm_fwd2p_kernel) for the input-gradient geometry when
+    // nothing is asked of the epilogue but the store (others: the one-tile-per-workgroup launch)
+    const bool pers = !a.scatter && !a.border && !a.bias && !a.flags && a.hs == 2 * a.ho && a.ws == 2 * a.wo &&
+                      a.cin % 64 == 0 && a.dyc == 0xa5 && a.dxc == 0x99 && !a.cin1 && a.M < (1L << 31) &&
+                      (2L * (256 / a.wo + 2) + 2) * a.ws * a.a_ld * 2 < (1L << 31);  // (a tile's source span: 32-bit offsets)
+    return {pers ? FWD2_PERS256 : FWD2_T256, 256, 256};
+  }
+  // 128 x 128 tiles with a 2-deep ring (64-68 KB, two workgroups per CU: one workgroup's
+  // prologue and LDS-staged epilogue overlap the other's MFMAs) for the bf16 Conv2DTranspose
+  // input gradient (up6/up7 0.87/1.93 -> 0.83/1.81 ms) and for every fp32 launch with
+  // N % 128 == 0 (inference dec6-dec8 15.4-15.8 -> 15.0-15.3 ms); launches with BN partial
+  // sums keep 256-row tiles (the sums rows are per 256 rows).
+  if (a.N % 128 == 0 && !a.stats && (!bf16 || tdgrad)) return {FWD2_T128, 128, 128};
+  return {FWD2_STAGED, 256, pick2(a.N).bn};
 }
 
-// ... as the persistent kernel (igemm_fwd2p_kernel) for the input-gradient geometry when
-// nothing is asked of the epilogue but the store (others: the one-tile-per-workgroup launch)
-bool fwd2_pers(const FwdArgs& a, bool bf16) {
-  return fwd2_t256(a, bf16) && !a.scatter && !a.border && !a.bias && !a.flags &&
-         a.hs == 2 * a.ho && a.ws == 2 * a.wo && a.cin % 64 == 0 && a.dyc == 0xa5 && a.dxc == 0x99 && !a.cin1 && a.M < (1L << 31) &&
-         (2L * (256 / a.wo + 2) + 2) * a.ws * a.a_ld * 2 < (1L << 31);  // (a tile's source span: 32-bit offsets)
+const char* fwd2_name(const FwdArgs& a, bool bf16) {
+  const Fwd2Plan pl = fwd2_plan(a, bf16);
+  static thread_local char buf[96];
+  snprintf(buf, sizeof(buf), "igemm_fwd2%s_kernel<%s,%dx%d>", pl.kind == FWD2_PERS256 ? "p" : "", bf16 ? "bf16" : "f32",
+           pl.bm, pl.bn);
+  return buf;
 }
 
-static int cu_count();
 // the bf16 Conv2DTranspose forward (bias or folded per-column bias, ReLU, inference affine,
 // BN partial sums) on tconv_fwd2p_kernel (others: tconv_stream / tconv_ws).  The plan
 // (tfwd2p_handles) depends on the sizes and flags only, so cnnitmo_tconv2x2_stat_rows (which asks
@@ -741,13 +744,13 @@ static int cu_count();
 // but requirements of the launch: a view that fails them is an error, never a silent fall-back to
 // a kernel with a different stat-row count.
 bool tfwd2p_handles(const FwdArgs& a, bool bf16) {
-  const int gx = std::max(cu_count() / 8, 1);
+  const int gx = std::max(cnnitmo_cu_count() / 8, 1);
   if (a.N <= 0 || a.M <= 0 || a.cin <= 0) return false;  // nothing to launch (and no gx % 0 below)
   return bf16 && a.scatter && a.ntaps == 1 && a.N % 256 == 0 && a.cin % 64 == 0 && a.cout % 8 == 0 &&
          !a.border && !(a.flags & ~(CNNITMO_RELU | CNNITMO_STATS | CNNITMO_BIAS_PER_COL | CNNITMO_AFFINE)) &&
          a.M < (1L << 31) && gx % (a.N / 256) == 0;
 }
-long tfwd2p_stat_rows(const FwdArgs& a) { return 8L * (std::max(cu_count() / 8, 1) / (a.N / 256)) * 2; }
+long tfwd2p_stat_rows(const FwdArgs& a) { return 8L * (std::max(cnnitmo_cu_count() / 8, 1) / (a.N / 256)) * 2; }
 int launch_tfwd2p(FwdArgs a, hipStream_t s, const char* what) {
   CNN_REQUIRE(tfwd2p_handles(a, true), "%s: unsupported by tconv_fwd2p", what);
   CNN_REQUIRE(a.a_off % 8 == 0 && a.a_ld % 8 == 0 && a.out_ld % 8 == 0 && a.out_off % 8 == 0,
@@ -757,7 +760,7 @@ int launch_tfwd2p(FwdArgs a, hipStream_t s, const char* what) {
   CNN_REQUIRE(!(a.flags & CNNITMO_STATS) || a.stats, "%s: STATS without buffer", what);
   a.mblocks = (int)((a.M + 255) / 256);
   a.nblocks = a.N / 256;
-  const int g = 8 * std::max(cu_count() / 8, 1);
+  const int g = 8 * std::max(cnnitmo_cu_count() / 8, 1);
   const int fl = a.flags & ~CNNITMO_BIAS_PER_COL;
   if (fl == (CNNITMO_RELU | CNNITMO_STATS))
     hipLaunchKernelGGL((tconv_fwd2p_kernel<256, 256, 2, 4, true>), dim3((unsigned)g), dim3(512), 0, s, a);
@@ -766,14 +769,11 @@ int launch_tfwd2p(FwdArgs a, hipStream_t s, const char* what) {
   return cnnitmo_check_launch(what);
 }
 
-static int cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return v;
-  }();
-  return n;
+// The sizes launch_fwd2 takes from dense views (its CNN_REQUIREs below; ve = Vec16<T>::N): the
+// queries give a shape that fails them no rows and no kernel name.
+bool fwd2_sizes_ok(const FwdArgs& a, int ve) {
+  return a.M > 0 && a.N > 0 && a.N % 32 == 0 && a.cin > 0 && a.cin % ve == 0 && a.a_ld % ve == 0 &&
+         a.out_ld % ve == 0 && (!a.scatter || a.cout % ve == 0);
 }
 
 template <typename T>
@@ -785,47 +785,34 @@ int launch_fwd2(FwdArgs a, hipStream_t s, const char* what) {
               "%s: views must be 16-byte aligned", what);
   CNN_REQUIRE(!a.scatter || a.cout % VE == 0, "%s: scatter needs cout %% %d == 0", what, VE);
   CNN_REQUIRE(a.M > 0 && a.ntaps >= 1 && a.ntaps <= 9, "%s: bad sizes", what);
-  const Cfg2 c = pick2(a.N);
-  if constexpr (sizeof(T) == 2) {
-    if (fwd2_pers(a, true)) {
-      a.mblocks = (int)((a.M + 255) / 256);
-      a.nblocks = a.N / 256;
-      const long t = (long)a.mblocks * a.nblocks;
-      CNN_REQUIRE(t < (1L << 31), "%s: grid too large", what);
-      CNN_REQUIRE((long)256 * a.out_ld * 2 + (long)a.N * 2 < (1L << 31), "%s: output row too wide", what);
-      const long g = 8 * std::min((long)std::max(cu_count() / 8, 1), (t + 7) / 8);  // one per CU, 8 | grid
-      hipLaunchKernelGGL((igemm_fwd2p_kernel<256, 256, 2, 4>), dim3((unsigned)g), dim3(512), 0, s, a);
-      return cnnitmo_check_launch(what);
-    }
-    if (fwd2_t256(a, true)) {
-      a.mblocks = (int)((a.M + 255) / 256);
-      a.nblocks = a.N / 256;
-      CNN_REQUIRE((long)a.mblocks * a.nblocks < (1L << 31), "%s: grid too large", what);
-      hipLaunchKernelGGL((igemm_fwd2_kernel<T, 256, 256, 2, 4, 2>), dim3((unsigned)(a.mblocks * a.nblocks)),
-                         dim3(512), 0, s, a);
-      return cnnitmo_check_launch(what);
-    }
-  }
-  if (fwd2_bm(a, sizeof(T) == 2) == 128) {
-    {
-      a.mblocks = (int)((a.M + 127) / 128);
-      a.nblocks = a.N / 128;
-      CNN_REQUIRE((long)a.mblocks * a.nblocks < (1L << 31), "%s: grid too large", what);
-      hipLaunchKernelGGL((igemm_fwd2_kernel<T, 128, 128, 2, 4, 2>), dim3((unsigned)(a.mblocks * a.nblocks)),
-                         dim3(512), 0, s, a);
-      return cnnitmo_check_launch(what);
-    }
-  }
-  a.mblocks = (int)((a.M + 255) / 256);
-  a.nblocks = a.N / c.bn;
+  const Fwd2Plan pl = fwd2_plan(a, sizeof(T) == 2);
+  a.mblocks = (int)((a.M + pl.bm - 1) / pl.bm);
+  a.nblocks = a.N / pl.bn;
   const long total = (long)a.mblocks * a.nblocks;
   CNN_REQUIRE(total < (1L << 31), "%s: grid too large", what);
   const dim3 grid((unsigned)total);
-  switch (c.bn) {
-    case 128: launch_st<T, 256, 128, 4, 2>(a, s, grid); break;
-    case 96: launch_st<T, 256, 96, 4, 1>(a, s, grid); break;
-    case 64: launch_st<T, 256, 64, 4, 1>(a, s, grid); break;
-    default: launch_st<T, 256, 32, 4, 1>(a, s, grid); break;
+  switch (pl.kind) {
+    case FWD2_PERS256:
+      if constexpr (sizeof(T) == 2) {  // (the plan: bf16 only)
+        CNN_REQUIRE((long)256 * a.out_ld * 2 + (long)a.N * 2 < (1L << 31), "%s: output row too wide", what);
+        const long g = 8 * std::min((long)std::max(cnnitmo_cu_count() / 8, 1), (total + 7) / 8);  // one per CU, 8 | grid
+        hipLaunchKernelGGL((igemm_fwd2p_kernel<256, 256, 2, 4>), dim3((unsigned)g), dim3(512), 0, s, a);
+      }
+      break;
+    case FWD2_T256:
+      if constexpr (sizeof(T) == 2)
+        hipLaunchKernelGGL((igemm_fwd2_kernel<T, 256, 256, 2, 4, 2>), grid, dim3(512), 0, s, a);
+      break;
+    case FWD2_T128:
+      hipLaunchKernelGGL((igemm_fwd2_kernel<T, 128, 128, 2, 4, 2>), grid, dim3(512), 0, s, a);
+      break;
+    default:
+      switch (pl.bn) {
+        case 128: launch_st<T, 256, 128, 4, 2>(a, s, grid); break;
+        case 96: launch_st<T, 256, 96, 4, 1>(a, s, grid); break;
+        case 64: launch_st<T, 256, 64, 4, 1>(a, s, grid); break;
+        default: launch_st<T, 256, 32, 4, 1>(a, s, grid); break;
+      }
   }
   return cnnitmo_check_launch(what);
 }

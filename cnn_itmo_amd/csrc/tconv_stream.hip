@@ -474,18 +474,6 @@ void ts_launch(const TSArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((tconv_stream_kernel<MODE, BN, ST, EPI>), dim3(grid), dim3(512), 0, s, a);
 }
 
-int num_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
-  return ncu;
-}
-
 }  // namespace
 
 bool tconv_stream_handles(int mode, int h, int w, int cin, int cout, bool epi) {
@@ -494,7 +482,7 @@ bool tconv_stream_handles(int mode, int h, int w, int cin, int cout, bool epi) {
 }
 
 // launch grid: 8 | grid and nblocks | grid / 8 (XCD-aware mapping in the kernel)
-int ts_grid(int nblocks) { return 8 * std::max(nblocks, num_cus() / 8 / nblocks * nblocks); }
+int ts_grid(int nblocks) { return 8 * std::max(nblocks, cnnitmo_cu_count() / 8 / nblocks * nblocks); }
 
 long tconv_stream_rows(int mode, int n, int h, int w, int cin, int cout, bool epi) {
   TSPlan pl;

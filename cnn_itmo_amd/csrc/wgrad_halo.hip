@@ -623,15 +623,7 @@ bool wh_plan(int n, int h, int w, int cin, int cout, WHPlan& pl, bool cat = fals
   const long per = (long)pl.strips * pl.cbm * pl.cbn;
   // whole rounds of resident workgroups: slots = CUs x workgroups per CU (LDS- or
   // register-limited); pick the row split with the least idle tail (fewest splits on ties)
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
-  if (cat && !(pl.bn == 96 && cin == 96 && pl.tw == 64)) return false;  // CAT: the [32 | 64] block only
+  if (cat &&!(pl.bn == 96 && cin == 96 && pl.tw == 64)) return false;  // CAT: the [32 | 64] block only
   const int xb = cat ? ((pl.tw + 2) * 64 + 1023) / 1024 + ((pl.tw + 2) * (pl.bn - 32) * 2 + 1023) / 1024
                      : ((pl.tw + 2) * pl.bn * 2 + 1023) / 1024,
             db = pl.tw * pl.bm * 2 / 1024;
@@ -643,7 +635,7 @@ bool wh_plan(int n, int h, int w, int cin, int cout, WHPlan& pl, bool cat = fals
   // workgroups per CU: the runtime's occupancy (the 64 x 64 block fits two by LDS but
   // one by registers: 12 waves at 114 VGPRs)
   const int occ = WH_OCC_API && !cat ? wh_occupancy(pl.bm, pl.bn, pl.tw) : std::max(1, (160 * 1024) / smem);
-  const long slots = (long)ncu * occ;
+  const long slots = (long)cnnitmo_cu_count() * occ;
   long best = 1;
   double best_eff = -1.0;
   for (long rs = 1; rs <= 64 && rs <= rows; ++rs) {
@@ -681,18 +673,10 @@ bool wh_plan_f32(int n, int h, int w, int cin, int cout, WHPlan& pl) {
   pl.cbn = cin / pl.bn;
   const long rows = (long)n * h;
   const long per = (long)pl.strips * pl.cbm * pl.cbn;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
   const int xb = (66 * pl.bn * 4 + 1023) / 1024, db = 64 * pl.bm * 4 / 1024;
   const int d = wf_ahead(pl.bm, pl.bn);
   const int smem = ((d + 4) * xb + (d + 1) * db) * 1024;  // WF32Cfg::SMEM (R = 1)
-  const long slots = (long)ncu * std::max(1, (160 * 1024) / smem);
+  const long slots = (long)cnnitmo_cu_count() * std::max(1, (160 * 1024) / smem);
   long best = 1;
   double best_eff = -1.0;
   for (long r = 1; r <= 64 && r <= rows; ++r) {

@@ -220,16 +220,8 @@ bool wt_plan(int n, int h, int w, int cin, int cout, WTPlan& pl) {
   pl.cbn = cin / pl.bn;
   const int nw = 2 * (pl.bm / 64) * (pl.bn / 64);
   pl.smem = (WT_D + 1) * (WT_TW * pl.bn * 2 + 2 * 2 * WT_TW * pl.bm * 2);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
   const int occ = std::max(1, std::min((160 * 1024) / pl.smem, 16 / nw));
-  const long slots = (long)ncu * occ;
+  const long slots = (long)cnnitmo_cu_count() * occ;
   const long rows = (long)n * h;
   const long per = (long)pl.strips * pl.cbm * pl.cbn;
   long best = 1;
@@ -415,11 +407,7 @@ bool wtf_plan(int n, int h, int w, int cin, int cout, WTPlan& pl) {
   pl.cbm = cout / WTF_BM;
   pl.cbn = cin / WTF_BN;
   pl.smem = WTF_SMEM;
-  int ncu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-  if (ncu <= 0) ncu = 256;
-  const long slots = ncu;
+  const long slots = cnnitmo_cu_count();
   const long rows = (long)n * h;
   const long per = (long)pl.strips * pl.cbm * pl.cbn;
   long best = 1;

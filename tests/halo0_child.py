@@ -1,7 +1,7 @@
 """Child process of test_gpu_ops.test_conv3x3_without_halo_kernel (not collected by pytest).
 
 CNNITMO_HALO is read once per process, so the implicit-GEMM fallback of the 3x3 conv
-(igemm_fwd_kernel, igemm_fwd2_kernel: dispatch() in igemm_fwd.hip) needs a process of its own.
+(igemm_fwd_kernel, igemm_fwd2_kernel: conv_route() in conv_dispatch.hip) needs a process of its own.
 With CNNITMO_HALO=0 this runs the existing checks, imported and not copied, at their own bounds:
 
   * test_gpu_ops.conv3x3_case (test_conv3x3_fwd_dgrad_wgrad's body) on kernel_cases.CONV3X3_HALO0;

@@ -1,6 +1,9 @@
 """Child processes of test_abi_and_host.py's host-query tests (not collected by pytest).
 
     python tests/host_query_child.py sweep     every host-only query over the argument grid
+    python tests/host_query_child.py values    the sweep's calls as "name(args) -> value" lines, with
+                                               n = 32 at the U-Net frame sizes and channel
+                                               counts up to 512 added: diff two libraries' output
     python tests/host_query_child.py launch    wgrad launches with channel counts below 32
     python tests/host_query_child.py names     kernel names as JSON (tests/kernel_cases.py),
                                                under whatever CNNITMO_HALO the parent set
@@ -25,6 +28,9 @@ QUERY = re.compile(r"cnnitmo_\w*(_rows|_workspace_bytes|_supported|_kernel_name)
 CH = (0, 1, 3, 8, 16, 24, 32, 40, 48, 64, 96, 128)
 HW = ((1, 1), (6, 10), (16, 64))
 M = (0, 1, 255, 1000)
+# added in the values mode: the bench's layers (n = 32 at each U-Net level) and wide layers
+UNET_HW = ((1088, 1920), (544, 960), (272, 480), (136, 240), (68, 120))
+CH_WIDE = CH + (160, 192, 256, 384, 512)
 # values of the parameters that are not part of a joint grid below, by their name in the header
 SINGLE = {"dtype": (0, 1), "n": (2,), "ntaps": (1, 4, 9), "dgrad": (0, 1), "with_grad": (0, 1), "scales": (1, 5),
           "m": M, "p": M, "rows": M, "ncols": CH, "c": CH, "cols": CH}
@@ -50,10 +56,10 @@ def header_params():
     return out
 
 
-def grid(params):
+def grid(params, ch=CH, hw=HW, n=None):
     """Argument tuples of one query: the product of its parameters' values.  Channel counts
-    go through the whole CH x CH grid; c1 (the first concat member) and the fused column range
-    (c0, c1) take a few values of their own."""
+    go through the whole ch x ch grid; c1 (the first concat member) and the fused column range
+    (c0, c1) take a few values of their own.  n: the batch sizes (default: SINGLE's)."""
     axes = []
     names = list(params)
     fused = "c0" in names
@@ -61,14 +67,16 @@ def grid(params):
         if p in ("h", "w"):
             continue
         if p in ("cin", "cout"):
-            axes.append(CH)
+            axes.append(ch)
+        elif p == "n" and n is not None:
+            axes.append(n)
         elif p == "c0":
             axes.append((0, 32))
         elif p == "c1":
             axes.append((-1, 0, 32) if fused else (0, 32, 64))  # -1: cin (every column above c0)
         else:
             axes.append(SINGLE[p])  # KeyError: a new query parameter needs its values here
-    shapes = HW if "h" in names else ((None, None),)
+    shapes = hw if "h" in names else ((None, None),)
 
     def rec(i, acc):
         if i == len(axes):
@@ -111,6 +119,19 @@ def sweep():
             if unsupported(name, dict(zip(params[name], args))):
                 assert not v, f"{name}{args} -> {v!r} for channel counts that no launch takes"
     say(f"done {calls}")
+
+
+def values():
+    L, lib = load_lib()
+    params = header_params()
+    for name in sorted(L.SIGNATURES):
+        if not QUERY.search(name):
+            continue
+        fn = getattr(lib, name)
+        calls = list(grid(params[name], CH_WIDE))
+        if "h" in params[name] and "n" in params[name]:
+            calls += grid(params[name], CH_WIDE, UNET_HW, (32,))
+        say("\n".join(f"{name}{args} -> {fn(*args)!r}" for args in calls))
 
 
 def unsupported(name, d):
@@ -177,4 +198,4 @@ def exact_names():
 
 
 if __name__ == "__main__":
-    {"sweep": sweep, "launch": launch, "names": names, "exact_names": exact_names}[sys.argv[1]]()
+    {"sweep": sweep, "values": values, "launch": launch, "names": names, "exact_names": exact_names}[sys.argv[1]]()

@@ -14,7 +14,7 @@ does not launch that direction.
 
 The name does not show everything: with BN partial sums (CNNITMO_STATS) the fp32 implicit GEMM
 runs 256-row tiles where cnnitmo_conv3x3_kernel_name, which asks for the inference forward,
-says 128x128 (fwd2_bm); the three store paths of the fused BN-backward dgrad are pinned by
+says 128x128 (fwd2_plan); the three store paths of the fused BN-backward dgrad are pinned by
 DGRAD_BN_BRANCH below.
 """
 DT = {"f32": 0, "bf16": 1}
@@ -297,7 +297,7 @@ TCONV_OPS = {  # test_gpu_ops.test_tconv
     },
     # the bf16 weight-stationary forward: the one 128-column block neither the streamed kernel (K = 512:
     # 64-column blocks) nor tconv_fwd2p (N % 256) takes; its dgrad on igemm_fwd2's 256 x 256 tiles, not the
-    # persistent kernel (32 channels per tap: fwd2_pers wants a multiple of 64); two row tiles
+    # persistent kernel (32 channels per tap: fwd2_plan wants a multiple of 64); two row tiles
     (512, 32, 9, 17): {
         "bf16": ("tconv_ws_kernel<0,128>", "igemm_fwd2_kernel<bf16,256x256>", "igemm_wgrad2_kernel<32,128,tpb4>"),
         "f32": ("tconv_ws_kernel<f32,0,64>", "igemm_fwd2_kernel<f32,128x128>", "igemm_wgrad_kernel<f32,32,128>"),
@@ -398,7 +398,7 @@ DGRAD_BN = {
     (64, 32, 17, 33, 0, 64, False): {"bf16": "halo_conv_kernel<64,2,wres>", "f32": "halo_conv_kernel<f32,64,2,wres>"},
 }
 
-# The store path of the fused dgrad, which the name does not show (conv_halo.hip, launch_cfg<T, BN, 2>):
+# The store path of the fused dgrad, which the name does not show (conv_halo.hip, halo_plan, EPI 2):
 #   allf = bnb_c1 == N && (bnb_c0 == 0 || (is bf16 && !res && bnb_c0 % BN == 0))
 # (N = cin, res = the ",wres" of the name, BN its block width); test_dgrad_bn_branches restates it
 # from the name of each row's DGRAD_BN case.  (cin, cout, c0, c1, dtype) -> branch
@@ -489,7 +489,7 @@ def expect_kernels(got, want):
 
 
 def dgrad_bn_branch(name, dt, cin, c0, c1):
-    """launch_cfg's choice restated from the kernel name (BN and wres) and the column range."""
+    """halo_plan's choice (HaloPlan::alt) restated from the kernel name (BN and wres) and the column range."""
     bn = int(name.split("<")[1].replace("f32,", "").split(",")[0])
     res = ",wres" in name
     if c1 == cin and c0 == 0:

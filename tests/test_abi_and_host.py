@@ -197,6 +197,39 @@ def test_tconv_planner_choices(lib):
     assert name(0, 8, 272, 480, 256, 128, 0).startswith(b"tconv_ws_kernel<f32")  # fp32: unchanged
 
 
+def test_rows_and_names_share_a_route(lib):
+    """The BN partial-sum rows query and the kernel-name query of an op answer from one route
+    (csrc/conv_dispatch.hip): over both dtypes, n = 2 and 32, eight frame sizes from 1x1 to the
+    bench's 1088x1920 and 17 x 17 channel counts (9 248 points) they say "no rows" and "no kernel"
+    together, for the conv3x3 and Conv2DTranspose forwards and the three fused BN-backward dgrads."""
+    import importlib.util
+    from cnn_itmo_amd import _lib
+    spec = importlib.util.spec_from_file_location("host_query_child", os.path.join(ROOT, "tests", "host_query_child.py"))
+    child = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(child)
+    q = _lib.query
+    points = 0
+    for dt in (0, 1):
+        for n in (2, 32):
+            for h, w in child.HW + child.UNET_HW:
+                for cin in child.CH_WIDE:
+                    for cout in child.CH_WIDE:
+                        points += 1
+                        at = (dt, n, h, w, cin, cout)
+                        pairs = [("conv3x3", q("cnnitmo_conv3x3_stat_rows", *at), q("cnnitmo_conv3x3_kernel_name", *at, 0)),
+                                 ("tconv2x2", q("cnnitmo_tconv2x2_stat_rows", *at), q("cnnitmo_tconv2x2_kernel_name", *at, 0)),
+                                 ("dgrad_bn_pooled", q("cnnitmo_conv3x3_dgrad_bn_pooled_rows", dt, n, h, w, cout, cin),
+                                  q("cnnitmo_conv3x3_dgrad_bn_pooled_kernel_name", dt, n, h, w, cout, cin)),
+                                 ("tconv_dgrad_bn", q("cnnitmo_tconv2x2_dgrad_bn_rows", dt, n, h, w, cout, cin),
+                                  q("cnnitmo_tconv2x2_dgrad_bn_kernel_name", dt, n, h, w, cout, cin))]
+                        pairs += [(f"dgrad_bn c0={c0}", q("cnnitmo_conv3x3_dgrad_bn_rows", dt, n, h, w, cout, cin, c0, cin),
+                                   q("cnnitmo_conv3x3_dgrad_bn_kernel_name", dt, n, h, w, cout, cin, c0, cin))
+                                  for c0 in (0, 32)]
+                        for op, rows, name in pairs:
+                            assert (rows == 0) == (not name), (op, at, rows, name)
+    assert points == 9248
+
+
 def run_child(mode, env=None, timeout=120):
     """One fresh python running tests/host_query_child.py <mode>; it prints every call before
     making it, so after an abnormal exit the last line names the call that killed it."""
@@ -250,7 +283,7 @@ def test_dispatch_coverage(lib):
 def test_case_lists_name_their_kernels(lib):
     """The name written next to each shared case is what the planner answers (the GPU tests
     assert the same before each launch; here without a GPU), and the fused dgrad's store path
-    table agrees with launch_cfg's condition restated from those names."""
+    table agrees with halo_plan's condition restated from those names."""
     from tests import kernel_cases as KC
     from cnn_itmo_amd import _lib
     q = _lib.query
