@@ -146,6 +146,10 @@ SIGNATURES = {
     "cnnitmo_lum_percentile": (i32, [vp, i32, i32, i32, vp, f64, vp, vp, i64, vp]),
     "cnnitmo_jpeg_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "cnnitmo_jpeg_roundtrip": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+    "cnnitmo_resize_coeffs": (i32, [i32, i32, i32, vp, vp]),
+    "cnnitmo_resize_tile_cols": (i32, [i32, i32, i32]),
+    "cnnitmo_resize_workspace_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
+    "cnnitmo_resize": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, f32, vp, vp]),
 }
 
 

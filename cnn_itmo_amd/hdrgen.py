@@ -48,6 +48,17 @@ target in fp32; ``'both'`` also rounds y (what the PNG route trains on); ``None`
 baseline-JPEG round trip on the GPU (``degrade.jpeg_roundtrip``'s kernel, ``jpeg_subsampling``
 ``'4:2:0'`` or ``'4:4:4'``), the compression the SDR material in the wild has been through.  The target
 y is never touched.  JPEG codes 8-bit samples, so ``quantize=None`` with it is a ``ValueError``.
+
+``flow_from_directory(..., max_side=N, resample='bilinear')``: a picture whose longer side exceeds
+``N`` is decoded when it is first loaded and made smaller once on the GPU, to
+``resize.fit_within(h, w, N)`` with the antialiased filter ``resample`` (``resize.resize``, PIL's
+arithmetic), and kept as an fp32 source; ``sizes``, the window draws and the "smaller than the
+window" check refer to the resized sizes.  So a 512 x 512 window shows a light source together with
+its surroundings, and no highlight falls between the taps of the pair kernel's bilinear gather.
+``'bicubic'`` and ``'lanczos'`` have negative lobes: their result is floored at 0, since negative
+radiance next to a highlight would make the log-average a NaN.  With ``max_side=None`` (default)
+nothing changes: the same draws, bits and launches.  With ``cache=False`` the decode and the
+resize repeat every time a picture is loaded.
 """
 from __future__ import annotations
 
@@ -57,7 +68,7 @@ import re
 
 import numpy as np
 
-from . import degrade, hdrio
+from . import degrade, hdrio, resize
 from .datagen import ImageDataGenerator, Iterator
 from .make_dataset import EXTENSIONS
 
@@ -142,17 +153,20 @@ class HDRPairGenerator:
         return q if u < self.jpeg_prob else 0
 
     def flow_from_directory(self, hdr_dir, target_size, window="random", window_size=None, batch_size=32,
-                            shuffle=True, seed=None, cache=True, workers=8, rank=None, world=None, output="cuda"):
-        """``batch_size`` is per rank; ``rank`` / ``world`` as ``ImageDataGenerator.flow_from_directory``."""
+                            shuffle=True, seed=None, cache=True, workers=8, rank=None, world=None, output="cuda",
+                            max_side=None, resample="bilinear"):
+        """``batch_size`` is per rank; ``rank`` / ``world`` as ``ImageDataGenerator.flow_from_directory``.
+        ``max_side`` / ``resample``: see the module's docstring; with ``cache=False`` a picture is
+        decoded and resized again every time it is loaded."""
         return HDRPairIterator(hdr_dir, self, target_size, window, window_size, batch_size, shuffle, seed, cache,
-                               workers, rank, world, output)
+                               workers, rank, world, output, max_side, resample)
 
 
 class HDRPairIterator(Iterator):
     """Yields ``(x, y)``: fp32 CUDA tensors [B, H, W, 3] (numpy arrays with ``output='numpy'``)."""
 
     def __init__(self, hdr_dir, gen, target_size, window, window_size, batch_size, shuffle, seed, cache, workers,
-                 rank=None, world=None, output="cuda"):
+                 rank=None, world=None, output="cuda", max_side=None, resample="bilinear"):
         if window not in ("random", "center", "full"):
             raise ValueError(f"window {window!r}: 'random', 'center' or 'full'")
         if output not in ("cuda", "numpy"):
@@ -164,7 +178,12 @@ class HDRPairIterator(Iterator):
         if not names:
             raise FileNotFoundError(f"no {'/'.join(EXTENSIONS)} files in {hdr_dir}")
         self.filenames = [os.path.join(hdr_dir, f) for f in names]
-        self.sizes = [image_size(f) for f in self.filenames]
+        self.file_sizes = self.sizes = [image_size(f) for f in self.filenames]
+        self.max_side, self.resample = max_side, resample
+        if max_side is not None:
+            if resample not in resize.FILTERS:
+                raise ValueError(f"resample {resample!r}: one of {', '.join(resize.FILTERS)}")
+            self.sizes = [resize.fit_within(hs, ws, max_side) for hs, ws in self.file_sizes]
         if window != "full":
             ch, cw = self.window_size
             for f, (hs, ws) in zip(self.filenames, self.sizes):
@@ -246,10 +265,21 @@ class HDRPairIterator(Iterator):
         if missing:
             import torch
             for j, a in zip(missing, arrays):
-                if tuple(a.shape[:2]) != self.sizes[j]:
+                if tuple(a.shape[:2]) != self.file_sizes[j]:
                     raise ValueError(f"{self.filenames[j]}: the picture changed size since its header was read")
-                have[j] = torch.from_numpy(a).cuda()
+                t = torch.from_numpy(a).cuda()
+                if self.sizes[j] != self.file_sizes[j]:
+                    t = self._shrink(t, self.sizes[j])
+                have[j] = t
         return have
+
+    def _shrink(self, t, size):
+        """A source in file format -> fp32 [oh,ow,3], resized once on the GPU."""
+        import torch
+        from . import ops
+        if t.dtype == torch.uint8:
+            t = ops.rgbe_decode(t, torch.empty(t.shape[:2] + (3,), dtype=torch.float32, device=t.device))
+        return resize.resize(t, size, self.resample, floor=0.0 if self.resample in resize.NEGATIVE_LOBES else None)
 
     def _batch(self, index_array):
         import torch

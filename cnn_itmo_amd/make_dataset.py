@@ -2,11 +2,13 @@
 (m-files/Reinhard.m for the targets, m-files/virtual_camera.m for the inputs).
 
     python -m cnn_itmo_amd.make_dataset --hdr-dir D [--out data/train] [--class-dir 0] \\
-        [--crop TOP,LEFT,SIZE] [--cameras K] [--seed S]
+        [--crop TOP,LEFT,SIZE] [--max-side N [--resample F]] [--cameras K] [--seed S]
 
 For every ``.hdr`` / ``.pic`` / ``.pfm`` file of D, in sorted order (file_index = 0, 1, ...):
 the image is read (hdrio.read_image), optionally cropped (tonemap.crop, 1-based MATLAB
-coordinates), and for k = 0..K-1
+coordinates), with ``--max-side N`` made to fit N (resize.fit_within) by the antialiased GPU
+resampler (resize.resize, filter F = box / bilinear / bicubic / lanczos, default bilinear; the
+last two floored at 0 so that no radiance is negative), and for k = 0..K-1
 
     out/output1/<class-dir>/<stem>_<k>.png = tonemap.reinhard(img, out_u8=True)             the target
     out/input1/<class-dir>/<stem>_<k>.png  = tonemap.virtual_camera(img, v, n, y, out_u8=True)  the input
@@ -27,10 +29,15 @@ import numpy as np
 EXTENSIONS = (".hdr", ".pic", ".pfm")
 
 
-def make_dataset(hdr_dir, out="data/train", class_dir="0", crop=None, cameras=1, seed=0, log=print):
-    """Returns the list of written pair names (``<stem>_<k>.png``)."""
+def make_dataset(hdr_dir, out="data/train", class_dir="0", crop=None, cameras=1, seed=0, log=print,
+                 max_side=None, resample="bilinear"):
+    """Returns the list of written pair names (``<stem>_<k>.png``).  ``max_side``: after the crop and
+    before the tone maps, a picture whose longer side exceeds it is resized on the GPU to
+    ``resize.fit_within(h, w, max_side)`` with the filter ``resample``."""
     from PIL import Image
-    from . import hdrio, tonemap
+    from . import hdrio, resize, tonemap
+    if max_side is not None and resample not in resize.FILTERS:
+        raise ValueError(f"resample {resample!r}: one of {', '.join(resize.FILTERS)}")
     files = sorted(f for f in os.listdir(hdr_dir) if os.path.splitext(f)[1].lower() in EXTENSIONS)
     if not files:
         raise FileNotFoundError(f"no {'/'.join(EXTENSIONS)} files in {hdr_dir}")
@@ -51,6 +58,11 @@ def make_dataset(hdr_dir, out="data/train", class_dir="0", crop=None, cameras=1,
             img = tonemap.crop(img, *crop)
             if img.shape[0] != crop[2] or img.shape[1] != crop[2]:
                 raise ValueError(f"{f}: crop {crop} does not fit a {full[1]}x{full[0]} image")
+        if max_side is not None:
+            size = resize.fit_within(int(img.shape[0]), int(img.shape[1]), max_side)
+            if size != tuple(img.shape[:2]):
+                img = resize.resize(img, size, resample,
+                                    floor=0.0 if resample in resize.NEGATIVE_LOBES else None)
         v, cn, cy = tonemap.virtual_camera_params(cameras, np.random.default_rng(seed + fi))
         target = tonemap.reinhard(img, out_u8=True)[0].cpu().numpy()
         for k in range(cameras):
@@ -72,13 +84,20 @@ def main(argv=None):
     ap.add_argument("--out", default="data/train")
     ap.add_argument("--class-dir", default="0", help="the class sub-directory flow_from_directory expects")
     ap.add_argument("--crop", default=None, help="TOP,LEFT,SIZE (1-based, as imcrop in Reinhard.m:10)")
+    ap.add_argument("--max-side", type=int, default=None,
+                    help="after --crop: resize a picture whose longer side exceeds N to fit it (antialiased, GPU)")
+    ap.add_argument("--resample", default="bilinear", choices=["box", "bilinear", "bicubic", "lanczos"],
+                    help="the filter of --max-side (PIL's arithmetic)")
     ap.add_argument("--cameras", type=int, default=1, help="virtual-camera inputs per HDR file")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
     crop = tuple(int(v) for v in a.crop.split(",")) if a.crop else None
     if crop is not None and len(crop) != 3:
         ap.error("--crop takes TOP,LEFT,SIZE")
-    names = make_dataset(a.hdr_dir, a.out, a.class_dir, crop, a.cameras, a.seed)
+    if a.max_side is not None and a.max_side < 1:
+        ap.error("--max-side takes a positive integer")
+    names = make_dataset(a.hdr_dir, a.out, a.class_dir, crop, a.cameras, a.seed, max_side=a.max_side,
+                         resample=a.resample)
     print(f"wrote {len(names)} pairs to {a.out}")
     return 0
 

@@ -706,3 +706,54 @@ def jpeg_roundtrip(x, qtabs, subsampling, apply=None, out=None, ws=None):
     call("cnnitmo_jpeg_roundtrip", ptr(x), n, h, w, JPEG_SUBSAMPLINGS[subsampling], qt.ctypes.data,
          None if ap is None else ap.ctypes.data, ptr(out), ptr(ws), ws.numel(), stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------- antialiased resampling
+RESIZE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}  # CNNITMO_RESIZE_*
+
+
+def resize_coeffs(n_in, n_out, filt):
+    """(bounds int32 [n_out,2] = (xmin, n), kk float64 [n_out,ksize]) of one axis, host arrays, from
+    cnnitmo_resize_coeffs: the one source of coefficients (needs no GPU).  filt: a RESIZE_FILTERS id."""
+    ksize = query("cnnitmo_resize_coeffs", int(n_in), int(n_out), int(filt), None, None)
+    if ksize < 0:
+        raise L.CnnItmoError(f"cnnitmo_resize_coeffs({n_in}, {n_out}, {filt}) failed ({ksize}): "
+                             f"{query('cnnitmo_last_error').decode(errors='replace')}")
+    bounds = np.empty((int(n_out), 2), np.int32)
+    kk = np.empty((int(n_out), ksize), np.float64)
+    rc = query("cnnitmo_resize_coeffs", int(n_in), int(n_out), int(filt), bounds.ctypes.data, kk.ctypes.data)
+    assert rc == ksize, (rc, ksize)
+    return bounds, kk
+
+
+def resize_tile_cols(w, ow, ksize_x):
+    """Output columns per tile of the horizontal pass; 0 = its direct (no LDS) path."""
+    return int(query("cnnitmo_resize_tile_cols", int(w), int(ow), int(ksize_x)))
+
+
+def resize_workspace_bytes(dtype, n, h, w, oh, ow):
+    return int(query("cnnitmo_resize_workspace_bytes", 0 if dtype == torch.float32 else 1, n, h, w, oh, ow))
+
+
+def resize(x, out, tab_x, tab_y, lo=float("-inf"), ws=None):
+    """x [n,h,w,3] -> out [n,oh,ow,3], contiguous device tensors, both fp32 or both uint8
+    (cnnitmo_resize).  tab_x / tab_y: (bounds int32 [o,2], kk float64 [o,ksize]) DEVICE tensors of
+    w -> ow / h -> oh, None for an axis that keeps its size."""
+    n, h, w, c = x.shape
+    oh, ow = int(out.shape[1]), int(out.shape[2])
+    assert c == 3 and x.dtype in (torch.float32, torch.uint8) and x.is_contiguous(), (x.dtype, tuple(x.shape))
+    assert out.dtype == x.dtype and out.is_contiguous() and tuple(out.shape) == (n, oh, ow, 3), tuple(out.shape)
+    args = []
+    for tab, o in ((tab_x, ow), (tab_y, oh)):
+        if tab is None:
+            args += [None, None, 0]
+            continue
+        b, k = tab
+        assert b.dtype == torch.int32 and b.is_contiguous() and tuple(b.shape) == (o, 2), (b.dtype, tuple(b.shape))
+        assert k.dtype == torch.float64 and k.is_contiguous() and k.shape[0] == o and k.data_ptr() % 8 == 0
+        args += [ptr(b), ptr(k), int(k.shape[1])]
+    if ws is None and w != ow and h != oh:
+        ws = workspace(resize_workspace_bytes(x.dtype, n, h, w, oh, ow), x.device)
+    call("cnnitmo_resize", ptr(x), 0 if x.dtype == torch.float32 else 1, n, h, w, ptr(out), oh, ow, *args,
+         float(lo), ptr(ws), stream_ptr())
+    return out

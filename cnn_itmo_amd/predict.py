@@ -148,8 +148,13 @@ def reference_log_average(ref_path):
 
 def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None, reference=None,
                 metrics_csv=None, hdr_dir=None, hdr_format="hdr", hdr_mode="script", hdr_key=0.18,
-                hdr_log_average=1.0, hdr_reference=None, hdr_metrics_csv=None, ms_ssim=False):
-    """``reference``: a directory of ground-truth PNGs; every written prediction is scored
+                hdr_log_average=1.0, hdr_reference=None, hdr_metrics_csv=None, ms_ssim=False, max_side=None,
+                resample="bilinear"):
+    """``max_side``: a frame whose longer side exceeds it is resized after loading, on the GPU, to
+    ``resize.fit_within(h, w, max_side)`` with the filter ``resample`` through the uint8 path, so the
+    network sees what ``PIL.Image.resize`` would have produced; the PNGs and HDR files written have
+    the resized size.
+    ``reference``: a directory of ground-truth PNGs; every written prediction is scored
     against the file of the same name there (PSNR / SSIM, logged per file and as the mean; a
     missing reference is reported and skipped, a size mismatch raises).  ``metrics_csv``:
     also write ``name;psnr;ssim`` rows to that file.  ``ms_ssim``: also score the multi-scale
@@ -186,6 +191,12 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
     want_float = hdr_dir is not None and hdr_mode == "exact"
     groups = {}
     frames = {f: read_png(f) for f in files}
+    if max_side is not None:
+        from . import resize
+        for f, u8 in frames.items():
+            size = resize.fit_within(u8.shape[0], u8.shape[1], max_side)
+            if size != tuple(u8.shape[:2]):
+                frames[f] = resize.resize(np.ascontiguousarray(u8), size, resample).cpu().numpy()
     for f in files:
         groups.setdefault(frames[f].shape, []).append(f)
     cache = {}
@@ -278,7 +289,14 @@ def main(argv=None):
                          "written reconstruction against the same-stem file (PQ PSNR and SSIM, hdrmetrics)")
     ap.add_argument("--hdr-metrics-csv", default=None,
                     help="with --hdr-reference: write name;psnr;ssim;scale_pred;scale_ref rows to this file")
+    ap.add_argument("--max-side", type=int, default=None,
+                    help="resize a frame whose longer side exceeds N to fit it before inference (antialiased, "
+                         "GPU, PIL's arithmetic on the 8-bit frame); the outputs have the resized size")
+    ap.add_argument("--resample", default="bilinear", choices=["box", "bilinear", "bicubic", "lanczos"],
+                    help="the filter of --max-side")
     a = ap.parse_args(argv)
+    if a.max_side is not None and a.max_side < 1:
+        ap.error("--max-side takes a positive integer")
     if a.metrics_csv and not a.reference:
         ap.error("--metrics-csv needs --reference")
     if a.ms_ssim and not a.reference:
@@ -298,7 +316,8 @@ def main(argv=None):
     out = predict_dir(m, a.input, a.output, a.batch, tile=tile, reference=a.reference, metrics_csv=a.metrics_csv,
                       hdr_dir=a.hdr, hdr_format=a.hdr_format, hdr_mode=a.hdr_mode, hdr_key=a.hdr_key,
                       hdr_log_average=a.hdr_log_average, hdr_reference=a.hdr_reference,
-                      hdr_metrics_csv=a.hdr_metrics_csv, ms_ssim=a.ms_ssim)
+                      hdr_metrics_csv=a.hdr_metrics_csv, ms_ssim=a.ms_ssim, max_side=a.max_side,
+                      resample=a.resample)
     print(f"wrote {len(out)} predictions to {a.output}")
     if a.hdr:
         print(f"wrote {len(out)} .{a.hdr_format} reconstructions to {a.hdr}")

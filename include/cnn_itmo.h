@@ -66,7 +66,8 @@ extern "C" {
  * cnnitmo_hdr_pairs / cnnitmo_hdr_pairs_workspace_bytes, cnnitmo_hdr_encode,
  * cnnitmo_lum_percentile / cnnitmo_lum_percentile_workspace_bytes,
  * cnnitmo_grad_sumsq / cnnitmo_grad_sumsq_workspace_bytes / cnnitmo_grad_clip,
- * cnnitmo_jpeg_roundtrip / cnnitmo_jpeg_workspace_bytes. */
+ * cnnitmo_jpeg_roundtrip / cnnitmo_jpeg_workspace_bytes,
+ * cnnitmo_resize / cnnitmo_resize_coeffs / cnnitmo_resize_workspace_bytes / cnnitmo_resize_tile_cols. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -810,6 +811,63 @@ long cnnitmo_jpeg_workspace_bytes(int n, int h, int w, int c /* chroma layout: t
 int cnnitmo_jpeg_roundtrip(const float* x, int n, int h, int w, int subsampling, const unsigned short* qtabs,
                            const unsigned char* apply, float* out, void* workspace, long workspace_bytes,
                            void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Antialiased separable resampling of n pictures x [n][h][w][3] -> out [n][oh][ow][3], fp32
+ * (dtype 0) or uint8 (dtype 1), with the arithmetic of Pillow's Image.resize (Resample.c);
+ * tests/resize_ref.py is the same in numpy, and the three agree bit for bit (uint8: byte for byte).
+ *
+ * Filters f(x), all in C double; `support` in brackets:
+ *   CNNITMO_RESIZE_BOX      (0.5)  1 for -0.5 < x <= 0.5, else 0
+ *   CNNITMO_RESIZE_BILINEAR (1)    1 - |x| for |x| < 1
+ *   CNNITMO_RESIZE_BICUBIC  (2)    a = -0.5: ((a+2)|x| - (a+3)) |x| |x| + 1 for |x| < 1,
+ *                                  (((|x| - 5)|x| + 8)|x| - 4) a for |x| < 2
+ *   CNNITMO_RESIZE_LANCZOS  (3)    sinc(x) sinc(x/3) for -3 <= x < 3; sinc(0) = 1, else
+ *                                  sin(t)/t with t = x * M_PI formed first (libm sin)
+ * cnnitmo_resize_coeffs (host, needs no GPU): the tables of one axis, `in` -> `out` samples:
+ *   scale = in/out; fs = max(scale, 1); sup = support fs; ksize = (int)ceil(sup) * 2 + 1;
+ *   for output sample xx: c = (xx + 0.5) scale; xmin = max((int)(c - sup + 0.5), 0);
+ *   xmax = min((int)(c + sup + 0.5), in); n = xmax - xmin;
+ *   k[x] = f((x + xmin - c + 0.5) * (1/fs)) for x < n, ww their sum in that order, k[x] /= ww when
+ *   ww != 0, the rest of the row 0.  bounds [out][2] = (xmin, n), kk [out][ksize].
+ *   Returns ksize; with bounds == kk == NULL it only returns ksize.  CNNITMO_EINVAL: a size < 1,
+ *   an unknown filter, exactly one of the two pointers null.
+ * One pass per axis whose size changes, the horizontal first, its result stored in the picture's
+ * type (fp32, or a clamped uint8) in the workspace; the vertical pass runs on that.
+ *   fp32:  ss = 0.0 (double); ss += (double)pixel[xmin + x] * k[x] for x = 0..n-1 in that order, a
+ *          multiply and then an add (no fused multiply-add); store (float)ss.
+ *   uint8: ki[x] = (int)(k[x] 2^22 + 0.5) for k[x] >= 0, (int)(k[x] 2^22 - 0.5) otherwise (made on
+ *          the device, exact in fp64); ss = 2^21 (int32); ss += pixel * ki[x];
+ *          store clamp(ss >> 22, 0, 255), `>>` the arithmetic shift.
+ * Equal sizes on both axes is a copy.  lo (fp32 only; pass -INFINITY with uint8): a floor applied
+ * where a value is stored to out (also by the copy), `v < lo ? lo : v`, so a NaN stays a NaN;
+ * -INFINITY is Pillow's behaviour.
+ * bounds_x / kk_x (ksize_x) are the tables of w -> ow, bounds_y / kk_y (ksize_y) those of h -> oh:
+ * DEVICE pointers, 4- and 8-byte aligned; those of an axis that keeps its size are not read and may
+ * be null.  Every index read from a table is clamped to the picture before it is used.
+ * x, out, workspace: device, 4-byte aligned for fp32, any alignment for uint8; the bits of out do
+ * not depend on further alignment.  workspace: cnnitmo_resize_workspace_bytes bytes, the
+ * intermediate [n][h][ow][3] picture; 0 (and the pointer unused) when fewer than two passes run, or
+ * for a shape the call refuses.  The query needs no GPU.
+ * cnnitmo_resize_tile_cols (host): the output columns per workgroup tile of the horizontal pass for
+ * these sizes, 0 when it takes the direct (no LDS) path: the source span of one column does not
+ * fit the staging buffer.  For tests and profiling labels.
+ * Stateless, never allocates, no atomics: bitwise reproducible.  CNNITMO_EINVAL before any launch,
+ * out untouched: an unknown dtype, a null x / out / table of a running pass / workspace of two
+ * passes, a size < 1, n*max(h,oh)*max(w,ow)*3 >= 2^31, a misaligned fp32 pointer, out or the
+ * workspace overlapping x or each other, a NaN lo or a floor with uint8, a ksize that is not
+ * (int)ceil(support * max(in/out, 1)) * 2 + 1 for one of the four supports.
+ */
+#define CNNITMO_RESIZE_BOX 0
+#define CNNITMO_RESIZE_BILINEAR 1
+#define CNNITMO_RESIZE_BICUBIC 2
+#define CNNITMO_RESIZE_LANCZOS 3
+int cnnitmo_resize_coeffs(int in, int out, int filter, int* bounds, double* kk);
+int cnnitmo_resize_tile_cols(int w, int ow, int ksize_x);
+long cnnitmo_resize_workspace_bytes(int dtype, int n, int h, int w, int rows /* oh */, int cols /* ow */);
+int cnnitmo_resize(const void* x, int dtype, int n, int h, int w, void* out, int oh, int ow, const int* bounds_x,
+                   const double* kk_x, int ksize_x, const int* bounds_y, const double* kk_y, int ksize_y, float lo,
+                   void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
