@@ -12,11 +12,11 @@ from .losses import DSSIM, MSSSIM, HighlightWeighted
 from .unet import ConvBN, ConvBNTranspose, TinyNet, U_net
 from .callbacks import (CSVLogger, EarlyStopping, LambdaCallback, LearningRateScheduler, ModelCheckpoint,
                         ReduceLROnPlateau, TerminateOnNaN)
-from . import degrade, hdrio, hdrmetrics, metrics, resize
+from . import degrade, exr, hdrio, hdrmetrics, metrics, resize
 from .hdrgen import HDRPairGenerator, HDRPairIterator
 
 __all__ = ["HDRPairGenerator", "HDRPairIterator","Activation", "BatchNormalization", "Concatenate", "Conv2D", "Conv2DTranspose", "Dropout",
            "Input", "InputLayer", "MaxPooling2D", "clear_session", "concatenate", "Model", "RMSprop",
            "Adam", "SGD", "DSSIM", "MSSSIM", "HighlightWeighted", "load_model", "ConvBN", "ConvBNTranspose", "TinyNet", "U_net", "CSVLogger",
            "LambdaCallback", "ModelCheckpoint", "LearningRateScheduler", "ReduceLROnPlateau", "EarlyStopping",
-           "TerminateOnNaN", "metrics", "hdrio", "hdrmetrics", "degrade", "resize"]
+           "TerminateOnNaN", "metrics", "hdrio", "hdrmetrics", "degrade", "resize", "exr"]

@@ -150,6 +150,10 @@ SIGNATURES = {
     "cnnitmo_resize_tile_cols": (i32, [i32, i32, i32]),
     "cnnitmo_resize_workspace_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
     "cnnitmo_resize": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, f32, vp, vp]),
+    "cnnitmo_exr_segment_bytes": (i32, []),
+    "cnnitmo_exr_workspace_bytes": (i64, [i32, i32, i64]),
+    "cnnitmo_exr_unpack": (i32, [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, i64, vp]),
+    "cnnitmo_exr_pack": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 

@@ -4,9 +4,9 @@
         [--align logmean|median|none] [--anchor key|percentile|FLOAT] [--key 0.18] \\
         [--white-nits 203] [--percentile 0.999] [--peak-nits 1000] [--ms-ssim] [--csv FILE]
 
-Every ``.hdr`` / ``.pic`` / ``.pfm`` file of ``--pred`` (sorted) is paired with the file of the
-same stem in ``--reference`` (any of the three extensions), both are read with
-``hdrio.read_image``, aligned, anchored to cd/m^2 and encoded, and PSNR / SSIM of the encoded
+Every ``.hdr`` / ``.pic`` / ``.pfm`` / ``.exr`` file of ``--pred`` (sorted) is paired with the file
+of the same stem in ``--reference`` (any of the four extensions), both are read with
+``hdrio.load_image``, aligned, anchored to cd/m^2 and encoded, and PSNR / SSIM of the encoded
 pair are printed per file and as the mean.  A missing reference is reported and skipped, a size
 mismatch is an error (as ``predict --reference``).  ``--csv``: also write
 ``name;psnr;ssim;scale_pred;scale_ref`` rows.  ``--ms-ssim``: also the multi-scale SSIM of the
@@ -22,7 +22,7 @@ import sys
 
 import numpy as np
 
-EXTENSIONS = (".hdr", ".pic", ".pfm")
+EXTENSIONS = (".hdr", ".pic", ".pfm", ".exr")
 CSV_HEADER = "name;psnr;ssim;scale_pred;scale_ref"
 
 
@@ -47,7 +47,7 @@ def score_files(pred_path, ref_path, encoding="pq", ms_ssim=False, **opts):
     from disk, and with ``ms_ssim`` a fifth value, hdrmetrics.hdr_ms_ssim; ``opts``:
     hdrmetrics.hdr_scales' keywords."""
     from . import hdrio, hdrmetrics, ops
-    p, r = hdrio.read_image(pred_path), hdrio.read_image(ref_path)
+    p, r = hdrio.load_image(pred_path), hdrio.load_image(ref_path)
     if p.shape != r.shape:
         raise ValueError(f"{ref_path}: reference is {r.shape[1]}x{r.shape[0]}, the prediction "
                          f"{os.path.basename(pred_path)} {p.shape[1]}x{p.shape[0]}")
@@ -106,7 +106,7 @@ def evaluate_dir(pred_dir, ref_dir, csv=None, log=print, encoding="pq", ms_ssim=
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--pred", required=True, help="directory of HDR reconstructions (.hdr / .pic / .pfm)")
+    ap.add_argument("--pred", required=True, help="directory of HDR reconstructions (.hdr / .pic / .pfm / .exr)")
     ap.add_argument("--reference", required=True, help="directory of ground-truth HDR files, paired by stem")
     ap.add_argument("--encoding", default="pq", choices=["pq", "log"])
     ap.add_argument("--align", default="logmean", choices=["logmean", "median", "none"],

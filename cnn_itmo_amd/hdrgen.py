@@ -4,7 +4,8 @@ The offline route (make_dataset, then two seed-locked ``ImageDataGenerator.flow_
 streams) writes 8-bit PNGs of ``tonemap.reinhard`` / ``tonemap.virtual_camera`` and re-decodes and
 warps them every epoch: targets quantised to 1/255, the camera draws frozen when the data set is
 built.  Here the HDR pictures stay on the device in their file format (RGBE bytes for ``.hdr`` /
-``.pic``, fp32 for ``.pfm``) and one ``cnnitmo_hdr_pairs`` call (csrc/hdrpairs.hip) makes a batch:
+``.pic``, fp32 for ``.pfm``; an ``.exr`` is unpacked to fp32 on the device once per load, exr.py)
+and one ``cnnitmo_hdr_pairs`` call (csrc/hdrpairs.hip) makes a batch:
 it gathers a warped window of each picture, takes its log-average and writes the virtual-camera
 input ``x`` and the Reinhard target ``y``.  No pixel is touched on the host.
 
@@ -68,7 +69,7 @@ import re
 
 import numpy as np
 
-from . import degrade, hdrio, resize
+from . import degrade, exr, hdrio, resize
 from .datagen import ImageDataGenerator, Iterator
 from .make_dataset import EXTENSIONS
 
@@ -76,7 +77,9 @@ QUANTIZE = {None: 0, "input": 1, "both": 3}
 
 
 def image_size(path):
-    """(h, w) of a ``.hdr`` / ``.pic`` / ``.pfm`` file from its header alone."""
+    """(h, w) of a ``.hdr`` / ``.pic`` / ``.pfm`` / ``.exr`` file from its header alone."""
+    if os.path.splitext(path)[1].lower() == ".exr":
+        return exr.exr_size(path)
     with open(path, "rb") as fh:
         buf = fh.read(1 << 16)
     if os.path.splitext(path)[1].lower() == ".pfm":
@@ -99,7 +102,11 @@ def image_size(path):
 
 def read_source(path):
     """A picture in its file format, row 0 = top: RGBE uint8 [h,w,4] (``.hdr`` / ``.pic``, as
-    hdrio.parse_hdr returns it) or float32 [h,w,3] (``.pfm``)."""
+    hdrio.parse_hdr returns it), float32 [h,w,3] (``.pfm``) or an exr.Parsed (``.exr``: the
+    inflated chunks, which the GPU unpacks to float32 [h,w,3] when the source is uploaded)."""
+    if os.path.splitext(path)[1].lower() == ".exr":
+        with open(path, "rb") as fh:
+            return exr.parse_exr(fh.read())
     if os.path.splitext(path)[1].lower() == ".pfm":
         return np.ascontiguousarray(hdrio.read_pfm(path))
     with open(path, "rb") as fh:
@@ -267,7 +274,7 @@ class HDRPairIterator(Iterator):
             for j, a in zip(missing, arrays):
                 if tuple(a.shape[:2]) != self.file_sizes[j]:
                     raise ValueError(f"{self.filenames[j]}: the picture changed size since its header was read")
-                t = torch.from_numpy(a).cuda()
+                t = exr.unpack(a) if isinstance(a, exr.Parsed) else torch.from_numpy(a).cuda()
                 if self.sizes[j] != self.file_sizes[j]:
                     t = self._shrink(t, self.sizes[j])
                 have[j] = t

@@ -34,6 +34,8 @@ Files:
   write_hdr(path, img, rle=True)          img: numpy array or CUDA tensor [h,w,3]
   read_pfm(path) -> numpy float32 [h,w,3]; write_pfm(path, img)       colour 'PF', bit-exact
   read_image(path) -> CUDA float32 [h,w,3]; write_image(path, img)    by extension
+  load_image(path) / save_image(path, img, **opts)    the same, and ``.exr`` through exr.py
+      (opts: write_exr's pixel_type / compression); the front ends use this pair
 
   Only the 4 bytes/pixel RGBE form crosses PCIe for ``.hdr``.  ``apply_exposure`` divides the
   decoded pixels by the header's EXPOSURE product (the file holds radiance * EXPOSURE).
@@ -319,3 +321,22 @@ def write_image(path, img):
     if e == ".pfm":
         return write_pfm(path, img)
     raise ValueError(f"{path}: unknown HDR image extension {e!r} (.hdr, .pic, .pfm)")
+
+
+def load_image(path):
+    """``.exr`` (exr.read_exr) or what read_image takes -> CUDA float32 [h,w,3]."""
+    if _ext(path) == ".exr":
+        from . import exr
+        return exr.read_exr(path)
+    return read_image(path)
+
+
+def save_image(path, img, **opts):
+    """numpy array or CUDA tensor [h,w,3] -> ``.exr`` (exr.write_exr with ``opts``: half ZIP by
+    default) or what write_image takes (no options)."""
+    if _ext(path) == ".exr":
+        from . import exr
+        return exr.write_exr(path, img, **opts)
+    if opts:
+        raise TypeError(f"{path}: options {sorted(opts)} are for .exr files")
+    return write_image(path, img)

@@ -4,8 +4,8 @@
     python -m cnn_itmo_amd.make_dataset --hdr-dir D [--out data/train] [--class-dir 0] \\
         [--crop TOP,LEFT,SIZE] [--max-side N [--resample F]] [--cameras K] [--seed S]
 
-For every ``.hdr`` / ``.pic`` / ``.pfm`` file of D, in sorted order (file_index = 0, 1, ...):
-the image is read (hdrio.read_image), optionally cropped (tonemap.crop, 1-based MATLAB
+For every ``.hdr`` / ``.pic`` / ``.pfm`` / ``.exr`` file of D, in sorted order (file_index = 0, 1, ...):
+the image is read (hdrio.load_image), optionally cropped (tonemap.crop, 1-based MATLAB
 coordinates), with ``--max-side N`` made to fit N (resize.fit_within) by the antialiased GPU
 resampler (resize.resize, filter F = box / bilinear / bicubic / lanczos, default bilinear; the
 last two floored at 0 so that no radiance is negative), and for k = 0..K-1
@@ -26,7 +26,7 @@ import sys
 
 import numpy as np
 
-EXTENSIONS = (".hdr", ".pic", ".pfm")
+EXTENSIONS = (".hdr", ".pic", ".pfm", ".exr")
 
 
 def make_dataset(hdr_dir, out="data/train", class_dir="0", crop=None, cameras=1, seed=0, log=print,
@@ -52,7 +52,7 @@ def make_dataset(hdr_dir, out="data/train", class_dir="0", crop=None, cameras=1,
     names = []
     rows = ["name;v;n;y"]
     for fi, (f, stem) in enumerate(zip(files, stems)):
-        img = hdrio.read_image(os.path.join(hdr_dir, f))
+        img = hdrio.load_image(os.path.join(hdr_dir, f))
         if crop is not None:
             full = tuple(img.shape[:2])
             img = tonemap.crop(img, *crop)
@@ -80,7 +80,7 @@ def make_dataset(hdr_dir, out="data/train", class_dir="0", crop=None, cameras=1,
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--hdr-dir", required=True, help="directory of .hdr / .pic / .pfm files")
+    ap.add_argument("--hdr-dir", required=True, help="directory of .hdr / .pic / .pfm / .exr files")
     ap.add_argument("--out", default="data/train")
     ap.add_argument("--class-dir", default="0", help="the class sub-directory flow_from_directory expects")
     ap.add_argument("--crop", default=None, help="TOP,LEFT,SIZE (1-based, as imcrop in Reinhard.m:10)")

@@ -757,3 +757,49 @@ def resize(x, out, tab_x, tab_y, lo=float("-inf"), ws=None):
     call("cnnitmo_resize", ptr(x), 0 if x.dtype == torch.float32 else 1, n, h, w, ptr(out), oh, ow, *args,
          float(lo), ptr(ws), stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------- OpenEXR pixels
+EXR_UINT, EXR_HALF, EXR_FLOAT = 0, 1, 2
+
+
+def exr_segment_bytes():
+    """Bytes of a chunk one workgroup of cnnitmo_exr_unpack's scan takes."""
+    return int(query("cnnitmo_exr_segment_bytes"))
+
+
+def exr_workspace_bytes(h, lines_per_chunk, line_bytes):
+    return int(query("cnnitmo_exr_workspace_bytes", int(h), int(lines_per_chunk), int(line_bytes)))
+
+
+def exr_unpack(raw, coded, lines_per_chunk, line_bytes, ch_off, ch_type, rgb, ws=None):
+    """raw uint8 [h * line_bytes] -> rgb [h,w,3] fp32, contiguous device tensors (cnnitmo_exr_unpack).
+    coded: device uint8 [chunks] or None (every chunk plain); ch_off / ch_type: host triples for
+    R, G, B.  ws: device uint8 workspace, allocated here when coded is given and ws is not."""
+    h, w, c = rgb.shape
+    assert c == 3 and rgb.dtype == torch.float32 and rgb.is_contiguous(), (rgb.dtype, tuple(rgb.shape))
+    assert raw.dtype == torch.uint8 and raw.is_contiguous() and raw.numel() == h * int(line_bytes), \
+        (raw.dtype, raw.numel(), h, line_bytes)
+    if coded is not None:
+        assert coded.dtype == torch.uint8 and coded.is_contiguous() and \
+            coded.numel() * int(lines_per_chunk) >= h, (coded.dtype, coded.numel())
+        if ws is None:
+            ws = workspace(exr_workspace_bytes(h, lines_per_chunk, line_bytes), raw.device)
+    off = (ctypes.c_int * 3)(*[int(v) for v in ch_off])
+    typ = (ctypes.c_int * 3)(*[int(v) for v in ch_type])
+    call("cnnitmo_exr_unpack", ptr(raw), ptr(coded), h, w, int(lines_per_chunk), int(line_bytes), off, typ,
+         ptr(rgb), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr())
+    return rgb
+
+
+def exr_pack(rgb, pixel_type, lines_per_chunk, coded, out):
+    """rgb [h,w,3] fp32 -> out uint8 [h * 3 * w * size]: lines of B, G, R values of pixel_type
+    (EXR_HALF / EXR_FLOAT), every chunk split and predicted when coded (cnnitmo_exr_pack)."""
+    h, w, c = rgb.shape
+    size = 2 if pixel_type == EXR_HALF else 4
+    assert c == 3 and rgb.dtype == torch.float32 and rgb.is_contiguous(), (rgb.dtype, tuple(rgb.shape))
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == h * 3 * w * size, \
+        (out.dtype, out.numel())
+    call("cnnitmo_exr_pack", ptr(rgb), h, w, int(pixel_type), int(lines_per_chunk), int(bool(coded)), ptr(out),
+         stream_ptr())
+    return out

@@ -126,7 +126,7 @@ def score_png(pred_u8, ref_path, ms_ssim=False):
 
 
 def write_hdr_prediction(path, pred_u8, pred_f32=None, mode="script", key=0.18, log_average=1.0):
-    """The HDR reconstruction of one prediction as ``path`` (.hdr or .pfm).  ``script``:
+    """The HDR reconstruction of one prediction as ``path`` (.hdr, .pfm or .exr: half, ZIP).  ``script``:
     inverse_Reinhard.m on the written 8-bit prediction; ``exact``: the algebraic inverse of
     Reinhard.m on the float prediction for the HDR log-average ``log_average``.  The inverse map
     and the RGBE encode run on the GPU; a .hdr leaves the device as 4 bytes per pixel."""
@@ -137,13 +137,13 @@ def write_hdr_prediction(path, pred_u8, pred_f32=None, mode="script", key=0.18, 
         hdr = tonemap.inverse_reinhard(np.ascontiguousarray(pred_f32), a=key, g=log_average, mode="exact")
     else:
         raise ValueError(f"hdr mode {mode!r} (script or exact)")
-    hdrio.write_image(path, hdr[0])
+    hdrio.save_image(path, hdr[0])
 
 
 def reference_log_average(ref_path):
     """The log-average luminance of the HDR file ref_path (``--hdr-log-average reference``)."""
     from . import hdrio, tonemap
-    return float(tonemap.log_average(hdrio.read_image(ref_path)).item())
+    return float(tonemap.log_average(hdrio.load_image(ref_path)).item())
 
 
 def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, tile=None, reference=None,
@@ -160,10 +160,11 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
     also write ``name;psnr;ssim`` rows to that file.  ``ms_ssim``: also score the multi-scale
     SSIM (images of at least 161 x 161 pixels), logged and as a further ``ms_ssim`` column.
     ``hdr_dir``: also write every prediction's HDR reconstruction there as ``name.hdr`` (Radiance
-    RGBE) or ``name.pfm`` (``hdr_format``); ``hdr_mode`` 'script' applies inverse_Reinhard.m to
-    the written 8-bit prediction, 'exact' the exact inverse of Reinhard.m (key ``hdr_key``,
-    log-average ``hdr_log_average``) to the float prediction.  The PNGs are the same either way.
-    ``hdr_reference``: a directory of ground-truth HDR files (.hdr / .pic / .pfm); every
+    RGBE), ``name.pfm`` or ``name.exr`` (OpenEXR: half, ZIP), by ``hdr_format``;
+    ``hdr_mode`` 'script' applies inverse_Reinhard.m to the written 8-bit prediction, 'exact' the
+    exact inverse of Reinhard.m (key ``hdr_key``, log-average ``hdr_log_average``) to the float
+    prediction.  The PNGs are the same either way.
+    ``hdr_reference``: a directory of ground-truth HDR files (.hdr / .pic / .pfm / .exr); every
     reconstruction written to ``hdr_dir`` is read back from disk and scored against the file of the
     same stem there (hdrmetrics.hdr_psnr_ssim with its defaults; logged per file and as the mean, a
     missing reference reported and skipped, a size mismatch raises).  ``hdr_metrics_csv``: also
@@ -171,8 +172,8 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
     mode, with ``hdr_reference``): each file's log-average is that of its reference."""
     from PIL import Image
     from . import evaluate_hdr as EH
-    if hdr_format not in ("hdr", "pfm"):
-        raise ValueError(f"hdr format {hdr_format!r} (hdr or pfm)")
+    if hdr_format not in ("hdr", "pfm", "exr"):
+        raise ValueError(f"hdr format {hdr_format!r} (hdr, pfm or exr)")
     if hdr_mode not in ("script", "exact"):
         raise ValueError(f"hdr mode {hdr_mode!r} (script or exact)")
     if hdr_reference is not None and hdr_dir is None:
@@ -216,7 +217,7 @@ def predict_dir(model, in_dir, out_dir, batch=8, pattern="*.png", log=print, til
                 hdr_dst = os.path.join(hdr_dir, f"{stem}.{hdr_format}")
                 hdr_ref = None if hdr_reference is None else EH.find_reference(hdr_reference, stem)
                 if from_reference and hdr_ref is None:
-                    raise FileNotFoundError(f"{os.path.basename(f)}: no reference {stem}.hdr/.pic/.pfm in "
+                    raise FileNotFoundError(f"{os.path.basename(f)}: no reference {stem}.hdr/.pic/.pfm/.exr in "
                                             f"{hdr_reference} to take the log-average from")
                 g = reference_log_average(hdr_ref) if from_reference else hdr_log_average
                 write_hdr_prediction(hdr_dst, p, pf, hdr_mode, hdr_key, g)
@@ -275,8 +276,8 @@ def main(argv=None):
                          "--metrics-csv)")
     ap.add_argument("--hdr", default=None, metavar="DIR",
                     help="also write each prediction's HDR reconstruction (inverse Reinhard) to DIR/name.hdr")
-    ap.add_argument("--hdr-format", default="hdr", choices=["hdr", "pfm"],
-                    help="Radiance RGBE (.hdr) or lossless PFM (.pfm)")
+    ap.add_argument("--hdr-format", default="hdr", choices=["hdr", "pfm", "exr"],
+                    help="Radiance RGBE (.hdr), lossless PFM (.pfm) or OpenEXR (.exr: half, ZIP)")
     ap.add_argument("--hdr-mode", default="script", choices=["script", "exact"],
                     help="script: inverse_Reinhard.m on the written 8-bit PNG; exact: the exact inverse of "
                          "Reinhard.m on the float prediction (no banding)")
@@ -285,7 +286,7 @@ def main(argv=None):
                     help="exact mode: the log-average luminance of the HDR image to reconstruct; 'reference' "
                          "(with --hdr-reference): that of each file's reference")
     ap.add_argument("--hdr-reference", default=None, metavar="DIR",
-                    help="with --hdr: directory of ground-truth HDR files (.hdr / .pic / .pfm); score each "
+                    help="with --hdr: directory of ground-truth HDR files (.hdr / .pic / .pfm / .exr); score each "
                          "written reconstruction against the same-stem file (PQ PSNR and SSIM, hdrmetrics)")
     ap.add_argument("--hdr-metrics-csv", default=None,
                     help="with --hdr-reference: write name;psnr;ssim;scale_pred;scale_ref rows to this file")

@@ -67,7 +67,8 @@ extern "C" {
  * cnnitmo_lum_percentile / cnnitmo_lum_percentile_workspace_bytes,
  * cnnitmo_grad_sumsq / cnnitmo_grad_sumsq_workspace_bytes / cnnitmo_grad_clip,
  * cnnitmo_jpeg_roundtrip / cnnitmo_jpeg_workspace_bytes,
- * cnnitmo_resize / cnnitmo_resize_coeffs / cnnitmo_resize_workspace_bytes / cnnitmo_resize_tile_cols. */
+ * cnnitmo_resize / cnnitmo_resize_coeffs / cnnitmo_resize_workspace_bytes / cnnitmo_resize_tile_cols,
+ * cnnitmo_exr_unpack / cnnitmo_exr_pack / cnnitmo_exr_workspace_bytes / cnnitmo_exr_segment_bytes. */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -868,6 +869,54 @@ long cnnitmo_resize_workspace_bytes(int dtype, int n, int h, int w, int rows /* 
 int cnnitmo_resize(const void* x, int dtype, int n, int h, int w, void* out, int oh, int ow, const int* bounds_x,
                    const double* kk_x, int ksize_x, const int* bounds_y, const double* kk_y, int ksize_y, float lo,
                    void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * OpenEXR scan-line pixels (the container and zlib are host work: cnn_itmo_amd/exr.py).
+ * A picture is h lines of line_bytes bytes; a line holds, channel after channel in the file's
+ * channel-list order, that channel's w values, little-endian: CNNITMO_EXR_UINT (4 bytes),
+ * CNNITMO_EXR_HALF (2), CNNITMO_EXR_FLOAT (4) -- the format's own type numbers.  Chunks of
+ * lines_per_chunk lines (1: NONE / ZIPS, 16: ZIP; the last chunk may be short) follow each other
+ * without gaps, chunk i at byte i * lines_per_chunk * line_bytes, n = its lines * line_bytes bytes.
+ * A coded chunk holds ZIP's form t of its record bytes r: t[k] = r[2k] for k < half = (n + 1) / 2,
+ * t[half + k] = r[2k + 1], then t[i] <- t[i] - t[i-1] + 128 (mod 256) left to right for i >= 1;
+ * a plain chunk holds r.
+ *
+ * cnnitmo_exr_unpack: raw (device, h * line_bytes bytes, any alignment) -> rgb [h][w][3] fp32
+ * (device, 4-byte aligned).  coded: device bytes [ceil(h / lines_per_chunk)], non-zero = coded, or
+ * null = every chunk plain.  ch_off / ch_type: HOST arrays of three: the byte offset of the red,
+ * green and blue channel inside a line and its type (the three may be one channel, a lone Y);
+ * they travel as kernel arguments.  Coded chunks are undone in the workspace (device,
+ * cnnitmo_exr_workspace_bytes, needed only with coded != null; it may hold anything): byte sums of
+ * segments of cnnitmo_exr_segment_bytes() bytes, then a scan per segment -- two launches, no
+ * waiting between workgroups -- then one launch gathers, converts and stores.  Conversions are
+ * done on the bits: HALF -> fp32 exact, denormals included, inf and NaN with the payload << 13;
+ * FLOAT copied; UINT -> fp32 rounded to nearest even.  Accesses are 16, 8 or 4 bytes wide where an
+ * address allows and single bytes otherwise: the same bits either way.  No address depends on a
+ * byte read from memory: a wrong `coded` flag gives wrong pixels, never a stray access.
+ *
+ * cnnitmo_exr_pack: rgb [h][w][3] fp32 -> out, h * 3 * w * size bytes: lines of the channels B, G,
+ * R (the file's name order) of pixel_type HALF or FLOAT, every chunk coded (coded = 1) or plain (0).
+ * fp32 -> HALF rounds to nearest even: 65520 and above -> inf, 2^-25 and below -> 0 with the sign,
+ * a NaN stays a NaN (its top ten payload bits, or 1 when those are zero).
+ *
+ * Stateless, never allocate, no atomics: bitwise reproducible.  CNNITMO_EINVAL before any launch,
+ * rgb / out untouched: a null raw / rgb / out / ch_off / ch_type, a null or short workspace with
+ * coded != null, h or w < 1, lines_per_chunk other than 1 or 16, a line_bytes that is odd, < 1 or
+ * >= 2^27, an unknown type, a channel offset that is odd or negative, a channel that runs past
+ * line_bytes, a coded flag other than 0 / 1, an rgb that is not 4-byte aligned.
+ * cnnitmo_exr_workspace_bytes(h, lines_per_chunk, line_bytes) (host, needs no GPU): 0 for sizes
+ * the launch refuses.
+ */
+#define CNNITMO_EXR_UINT 0
+#define CNNITMO_EXR_HALF 1
+#define CNNITMO_EXR_FLOAT 2
+int cnnitmo_exr_segment_bytes(void);
+long cnnitmo_exr_workspace_bytes(int h, int rows /* lines_per_chunk */, long cols /* line_bytes */);
+int cnnitmo_exr_unpack(const uint8_t* raw, const uint8_t* coded, int h, int w, int lines_per_chunk, long line_bytes,
+                       const int* ch_off, const int* ch_type, float* rgb, void* workspace, long workspace_bytes,
+                       void* stream);
+int cnnitmo_exr_pack(const float* rgb, int h, int w, int pixel_type, int lines_per_chunk, int coded, uint8_t* out,
+                     void* stream);
 
 #ifdef __cplusplus
 }
