@@ -141,6 +141,9 @@ SIGNATURES = {
     "cnnitmo_rgbe_decode": (i32, [vp, i64, vp, vp]),
     "cnnitmo_hdr_pairs_workspace_bytes": (sz, [i32]),
     "cnnitmo_hdr_pairs": (i32, [vp, i32, i32, i32, vp, vp, vp, f64, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "cnnitmo_hdr_pairs_sensor": (i32, [vp, i32, i32, i32, vp, vp, vp, f64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                       sz, vp]),
+    "cnnitmo_sensor_noise": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "cnnitmo_hdr_encode": (i32, [i32, vp, i32, i32, i32, vp, vp, vp]),
     "cnnitmo_lum_percentile_workspace_bytes": (i64, [i32]),
     "cnnitmo_lum_percentile": (i32, [vp, i32, i32, i32, vp, f64, vp, vp, i64, vp]),

@@ -1,4 +1,5 @@
-// Training pairs straight from HDR pictures: cnnitmo_hdr_pairs.
+// Training pairs straight from HDR pictures: cnnitmo_hdr_pairs, cnnitmo_hdr_pairs_sensor and the
+// stand-alone cnnitmo_sensor_noise.
 //
 // For every output frame i a descriptor names a source picture (fp32 RGB or RGBE bytes, any size)
 // and a clamp window inside it.  Per output pixel (r, c):
@@ -12,6 +13,14 @@
 //   target y_c = hdr_c * (L / Y),  X = key/G * Y,        L = X / (1 + X)                     (Reinhard.m)
 //   input  x_c = hdr_c * (L / Y),  X = cam[i][0]/G * Y,  L = min(1, (1+n) X^y / (n + X^y))   (virtual_camera.m)
 //   store: NaN -> 0, clamp to [0, 1]; (float)v, or when quantised (float)uint8(255 v) * (float)(1/255)
+//
+// cnnitmo_hdr_pairs_sensor, response 1 (a sensor clips every channel at its own full well, so an
+// overexposed colour goes to white; the curve above clips the luminance and keeps the hue):
+//   e_c  = cam[i][0]/G * hdr_c                                   exposure in units of full well
+//   e'_c = max(0, e_c + sqrt(a max(e_c, 0) + b^2) z_c)           only with noise[i] = (a, b) != (0, 0);
+//                                                                z from Philox4x64-10, sensor_px.h
+//   x_c  = min(1, (1+n) e'_c^y / (n + e'_c^y))                   the same store; y is untouched
+// Response 0 without noise is cnnitmo_hdr_pairs, the same instantiation of the same kernel.
 //
 // The arithmetic after the gather is tonemap.hip's (float64, no FMA contraction); the gather is
 // augment.hip's formula.  Contraction is off for the whole file, so the two passes below, which
@@ -31,6 +40,7 @@
 // No atomics: the reduction is a fixed partition and a fixed-order fold, bitwise reproducible.
 #include "common.h"
 #include "rgbe_px.h"
+#include "sensor_px.h"   // sensor_normals, sensor_noisy
 #include "tonemap_px.h"  // Lum, lum, REALMIN, im2uint8, lum_of
 
 #include <limits.h>
@@ -149,13 +159,26 @@ __device__ __forceinline__ void store_tile(float* __restrict__ dst, const float*
   for (int j = threadIdx.x; j < nfl; j += TB) dst[j] = tile[j];
 }
 
+// the camera curve of virtual_camera.m on one exposure
+__device__ __forceinline__ double camera_curve(double X, double cn, double cy) {
+  const double Xy = pow(X, cy);
+  return fmin(1.0, (1.0 + cn) * (Xy / (cn + Xy)));
+}
+
+// RESPONSE 0: the curve acts on the luminance, the three channels share its factor; 1: on every
+// channel's own exposure.  NOISY (RESPONSE 1 only): sensor noise on the exposures, noise [n][2] =
+// (a, b) and keys [n][2] per frame; a frame with a = b = 0 takes the path without noise.
+template <int RESPONSE, bool NOISY>
 __global__ __launch_bounds__(TB) void hdr_pairs_apply(const cnnitmo_hdr_src* __restrict__ srcs, int h, int w,
                                                       const double* __restrict__ mats,
                                                       const int* __restrict__ flips, Lum lc, double key,
                                                       const double* __restrict__ cam,
                                                       const double* __restrict__ G, int quantize,
-                                                      float* __restrict__ x, float* __restrict__ y,
-                                                      float* __restrict__ warped, long total) {
+                                                      const double* __restrict__ noise,
+                                                      const uint64_t* __restrict__ keys, float* __restrict__ x,
+                                                      float* __restrict__ y, float* __restrict__ warped,
+                                                      long total) {
+  static_assert(RESPONSE == 1 || !NOISY, "the noise model is defined on channel exposures");
   __shared__ float sx[3 * TB], sy[3 * TB], sw[3 * TB];
   const long base = (long)blockIdx.x * TB;
   const long i = base + threadIdx.x;
@@ -174,13 +197,29 @@ __global__ __launch_bounds__(TB) void hdr_pairs_apply(const cnnitmo_hdr_src* __r
     const double ft = (Xt / (1.0 + Xt)) / Y;
     // input: virtual_camera.m
     const double cn = cam[3 * (long)im + 1], cy = cam[3 * (long)im + 2];
-    const double Xc = (cam[3 * (long)im] / g) * Y;
-    const double Xy = pow(Xc, cy);
-    const double fx = fmin(1.0, (1.0 + cn) * (Xy / (cn + Xy))) / Y;
     const int t = 3 * threadIdx.x;
-    sx[t] = finish(R * fx, quantize & 1);
-    sx[t + 1] = finish(Gc * fx, quantize & 1);
-    sx[t + 2] = finish(B * fx, quantize & 1);
+    if (RESPONSE == 0) {
+      const double Xc = (cam[3 * (long)im] / g) * Y;
+      const double Xy = pow(Xc, cy);
+      const double fx = fmin(1.0, (1.0 + cn) * (Xy / (cn + Xy))) / Y;
+      sx[t] = finish(R * fx, quantize & 1);
+      sx[t + 1] = finish(Gc * fx, quantize & 1);
+      sx[t + 2] = finish(B * fx, quantize & 1);
+    } else {
+      const double dt = cam[3 * (long)im] / g;
+      double e[3] = {dt * R, dt * Gc, dt * B};
+      if (NOISY) {
+        const double a = noise[2 * (long)im], b = noise[2 * (long)im + 1];
+        if (a != 0.0 || b != 0.0) {  // uniform over a frame
+          double z[3];
+          sensor_normals(keys[2 * (long)im], keys[2 * (long)im + 1], (uint64_t)rem, z);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) e[k] = fmax(0.0, sensor_noisy(e[k], a, b, z[k]));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sx[t + k] = finish(camera_curve(e[k], cn, cy), quantize & 1);
+    }
     sy[t] = finish(R * ft, quantize & 2);
     sy[t + 1] = finish(Gc * ft, quantize & 2);
     sy[t + 2] = finish(B * ft, quantize & 2);
@@ -198,6 +237,36 @@ __global__ __launch_bounds__(TB) void hdr_pairs_apply(const cnnitmo_hdr_src* __r
   if (warped) store_tile(warped + 3 * base, sw, nfl);
 }
 
+// out = (float)sensor_noisy(e, a, b, z) of every channel value, unclamped.  One thread makes the
+// three normals of one pixel into LDS; then consecutive lanes take consecutive floats of the block's
+// 3 * TB, so a wave instruction reads and writes 256 contiguous bytes.
+__global__ __launch_bounds__(TB) void sensor_noise_kernel(const float* __restrict__ e, long hw,
+                                                          const double* __restrict__ noise,
+                                                          const uint64_t* __restrict__ keys,
+                                                          float* __restrict__ out, long total) {
+  __shared__ double sz[3 * TB];
+  const long base = (long)blockIdx.x * TB;
+  const long i = base + threadIdx.x;
+  if (i < total) {
+    const long im = i / hw;
+    double z[3] = {0.0, 0.0, 0.0};
+    if (noise[2 * im] != 0.0 || noise[2 * im + 1] != 0.0)
+      sensor_normals(keys[2 * im], keys[2 * im + 1], (uint64_t)(i - im * hw), z);
+    sz[3 * threadIdx.x] = z[0];
+    sz[3 * threadIdx.x + 1] = z[1];
+    sz[3 * threadIdx.x + 2] = z[2];
+  }
+  __syncthreads();
+  const long left = total - base;
+  const int nfl = 3 * (int)(left < TB ? left : TB);
+  for (int j = threadIdx.x; j < nfl; j += TB) {
+    const long im = (base + j / 3) / hw;
+    const double a = noise[2 * im], b = noise[2 * im + 1];
+    const float v = e[3 * base + j];
+    out[3 * base + j] = a != 0.0 || b != 0.0 ? (float)sensor_noisy((double)v, a, b, sz[j]) : v;
+  }
+}
+
 }  // namespace
 
 // part [n][PARTS], then G [n]
@@ -205,17 +274,23 @@ extern "C" size_t cnnitmo_hdr_pairs_workspace_bytes(int n) {
   return n > 0 ? (size_t)n * (PARTS + 1) * sizeof(double) : 0;
 }
 
-extern "C" int cnnitmo_hdr_pairs(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats,
-                                 const int* flips, const double* lum_coef, double key, const double* cam,
-                                 int quantize, float* x, float* y, float* warped, double* logsum, void* workspace,
-                                 size_t ws_bytes, void* stream) {
-  CNN_REQUIRE(srcs && mats && flips && cam && x && y && workspace, "hdr_pairs: null pointer");
-  CNN_REQUIRE(n > 0 && h > 0 && w > 0, "hdr_pairs: bad shape %d x %d x %d", n, h, w);
-  CNN_REQUIRE(n <= 65535, "hdr_pairs: n %d > 65535 frames", n);
-  CNN_REQUIRE((long)h * w <= INT_MAX && (long)n * h * w < (1L << 38), "hdr_pairs: too large");
-  CNN_REQUIRE((quantize & ~3) == 0, "hdr_pairs: quantize %d", quantize);
-  CNN_REQUIRE(ws_bytes >= cnnitmo_hdr_pairs_workspace_bytes(n), "hdr_pairs: workspace too small");
-  CNN_REQUIRE(((uintptr_t)workspace & 7) == 0, "hdr_pairs: workspace is not 8-byte aligned");
+// the three launches of both entry points; `who` names the entry in error messages
+static int hdr_pairs_run(const char* who, const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats,
+                         const int* flips, const double* lum_coef, double key, const double* cam, int quantize,
+                         int response, const double* noise, const uint64_t* keys, float* x, float* y, float* warped,
+                         double* logsum, void* workspace, size_t ws_bytes, void* stream) {
+  CNN_REQUIRE(srcs && mats && flips && cam && x && y && workspace, "%s: null pointer", who);
+  CNN_REQUIRE(n > 0 && h > 0 && w > 0, "%s: bad shape %d x %d x %d", who, n, h, w);
+  CNN_REQUIRE(n <= 65535, "%s: n %d > 65535 frames", who, n);
+  CNN_REQUIRE((long)h * w <= INT_MAX && (long)n * h * w < (1L << 38), "%s: too large", who);
+  CNN_REQUIRE((quantize & ~3) == 0, "%s: quantize %d", who, quantize);
+  CNN_REQUIRE(response == 0 || response == 1, "%s: response %d", who, response);
+  CNN_REQUIRE(!noise || response == 1, "%s: noise needs response 1, the model is defined on channel exposures",
+              who);
+  CNN_REQUIRE(!noise || keys, "%s: noise without keys", who);
+  CNN_REQUIRE((((uintptr_t)noise | (uintptr_t)keys) & 7) == 0, "%s: noise or keys not 8-byte aligned", who);
+  CNN_REQUIRE(ws_bytes >= cnnitmo_hdr_pairs_workspace_bytes(n), "%s: workspace too small", who);
+  CNN_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace is not 8-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   const Lum lc = lum_of(lum_coef);
   double* part = (double*)workspace;
@@ -224,7 +299,38 @@ extern "C" int cnnitmo_hdr_pairs(const cnnitmo_hdr_src* srcs, int n, int h, int 
   hipLaunchKernelGGL(hdr_logsum_partial, dim3(PARTS, n), dim3(TB), 0, s, srcs, h, w, mats, flips, lc, part);
   hipLaunchKernelGGL(hdr_logsum_fold, dim3((n + 63) / 64), dim3(64), 0, s, (const double*)part, n,
                      1.0 / (double)hw, G, logsum);
-  hipLaunchKernelGGL(hdr_pairs_apply, dim3((unsigned)((total + TB - 1) / TB)), dim3(TB), 0, s, srcs, h, w, mats,
-                     flips, lc, key, cam, (const double*)G, quantize, x, y, warped, total);
-  return cnnitmo_check_launch("hdr_pairs");
+  auto* apply = response == 0 ? hdr_pairs_apply<0, false> : noise ? hdr_pairs_apply<1, true> : hdr_pairs_apply<1, false>;
+  hipLaunchKernelGGL(apply, dim3((unsigned)((total + TB - 1) / TB)), dim3(TB), 0, s, srcs, h, w, mats, flips, lc, key,
+                     cam, (const double*)G, quantize, noise, keys, x, y, warped, total);
+  return cnnitmo_check_launch(who);
+}
+
+extern "C" int cnnitmo_hdr_pairs(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats,
+                                 const int* flips, const double* lum_coef, double key, const double* cam,
+                                 int quantize, float* x, float* y, float* warped, double* logsum, void* workspace,
+                                 size_t ws_bytes, void* stream) {
+  return hdr_pairs_run("hdr_pairs", srcs, n, h, w, mats, flips, lum_coef, key, cam, quantize, 0, nullptr, nullptr, x,
+                       y, warped, logsum, workspace, ws_bytes, stream);
+}
+
+extern "C" int cnnitmo_hdr_pairs_sensor(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats,
+                                        const int* flips, const double* lum_coef, double key, const double* cam,
+                                        int quantize, int response, const double* noise, const uint64_t* keys,
+                                        float* x, float* y, float* warped, double* logsum, void* workspace,
+                                        size_t ws_bytes, void* stream) {
+  return hdr_pairs_run("hdr_pairs_sensor", srcs, n, h, w, mats, flips, lum_coef, key, cam, quantize, response, noise,
+                       keys, x, y, warped, logsum, workspace, ws_bytes, stream);
+}
+
+extern "C" int cnnitmo_sensor_noise(const float* e, int n, int h, int w, const double* noise, const uint64_t* keys,
+                                    float* out, void* stream) {
+  CNN_REQUIRE(e && noise && keys && out, "sensor_noise: null pointer");
+  CNN_REQUIRE(n > 0 && h > 0 && w > 0, "sensor_noise: bad shape %d x %d x %d", n, h, w);
+  CNN_REQUIRE((long)h * w <= INT_MAX && (long)n * h * w < (1L << 38), "sensor_noise: too large");
+  CNN_REQUIRE((((uintptr_t)noise | (uintptr_t)keys) & 7) == 0 && (((uintptr_t)e | (uintptr_t)out) & 3) == 0,
+              "sensor_noise: misaligned pointer");
+  const long hw = (long)h * w, total = (long)n * hw;
+  hipLaunchKernelGGL(sensor_noise_kernel, dim3((unsigned)((total + TB - 1) / TB)), dim3(TB), 0, (hipStream_t)stream,
+                     e, hw, noise, keys, out, total);
+  return cnnitmo_check_launch("sensor_noise");
 }

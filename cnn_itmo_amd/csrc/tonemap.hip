@@ -5,6 +5,8 @@
 //                           X = (0.18/G) * Y; L = X/(1+X); sdr_c = hdr_c * (L / Y)
 //   virtual_camera.m:10-31  X = (0.18*2^v/G) * Y; X = min(1, (1+n)*(X^y/(n+X^y)))
 //                           sdr_c = hdr_c * (X / Y)
+//   (per-channel response)  X_c = (0.18*2^v/G) * hdr_c; sdr_c = min(1, (1+n)*(X_c^y/(n+X_c^y))):
+//                           not in the reference; what cnnitmo_hdr_pairs_sensor's response 1 computes
 //   inverse_Reinhard.m:1-23 In = (u8/255)^2.2; I = RGB2Lum(In); X = I/(I-1)
 //                           G_X = exp(sum(log(max(X, realmin))) * (1/(H*W)))
 //                           G_E = exp(P*log(G_X)/PB1 - PB2*log(a)/PB1)  (PB1/PB2: #I==0 / #I~=0)
@@ -87,7 +89,8 @@ __global__ __launch_bounds__(BLK_PER_IMG) void stats_final_kernel(const double* 
   }
 }
 
-// curve 0: Reinhard; 1: virtual camera.  params per image: [key*2^v, n, y]
+// curve 0: Reinhard; 1: virtual camera; 1 | CNNITMO_CURVE_PER_CHANNEL: virtual camera with a per-channel
+// response.  params per image: [key*2^v, n, y]
 __global__ __launch_bounds__(TB) void tonemap_kernel(int curve, const float* __restrict__ hdr, int n, long hw,
                                                      Lum lc, const double* __restrict__ params,
                                                      const double* __restrict__ stats, int out_u8,
@@ -101,6 +104,28 @@ __global__ __launch_bounds__(TB) void tonemap_kernel(int curve, const float* __r
   const double R = q[0], Gc = q[1], B = q[2];
   const double Y = lum(lc, R, Gc, B);
   double X = dt * Y, L;
+  if (curve == (1 | CNNITMO_CURVE_PER_CHANNEL)) {  // the curve on every channel's own exposure: each clips alone
+    const double cn = params[3 * im + 1], cy = params[3 * im + 2];
+    const double e[3] = {dt * R, dt * Gc, dt * B};
+    double o[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double ey = pow(e[k], cy);
+      o[k] = fmin(1.0, (1.0 + cn) * (ey / (cn + ey)));
+    }
+    if (out_u8) {
+      uint8_t* q8 = (uint8_t*)out + i * 3;
+      q8[0] = im2uint8(o[0]);
+      q8[1] = im2uint8(o[1]);
+      q8[2] = im2uint8(o[2]);
+    } else {
+      float* qf = (float*)out + i * 3;
+      qf[0] = (float)o[0];
+      qf[1] = (float)o[1];
+      qf[2] = (float)o[2];
+    }
+    return;
+  }
   if (curve == 0) {
     L = X / (1.0 + X);
   } else {
@@ -181,7 +206,7 @@ extern "C" int cnnitmo_tonemap_stats(int mode, const void* img, int n, int h, in
 extern "C" int cnnitmo_tonemap_apply(int curve, const float* hdr, int n, int h, int w, const double* lum_coef,
                                      const double* params, const double* stats, int out_u8, void* out,
                                      void* stream) {
-  CNN_REQUIRE(curve == 0 || curve == 1, "tonemap_apply: curve %d", curve);
+  CNN_REQUIRE(curve == 0 || curve == 1 || curve == (1 | CNNITMO_CURVE_PER_CHANNEL), "tonemap_apply: curve %d", curve);
   CNN_REQUIRE(hdr && params && stats && out, "tonemap_apply: null pointer");
   CNN_REQUIRE(n > 0 && h > 0 && w > 0, "tonemap_apply: bad shape");
   const long hw = (long)h * w, tot = (long)n * hw;

@@ -1,4 +1,4 @@
-"""Degradations of SDR inputs on the GPU: the baseline-JPEG round trip.
+"""Degradations of SDR inputs on the GPU: the baseline-JPEG round trip and sensor noise.
 
 The SDR pictures an inverse tone-mapping network meets have been through JPEG; a network trained on
 clean quantised inputs expands their blocking and ringing into the highlights it invents.
@@ -11,6 +11,17 @@ touching the host:
     x = degrade.jpeg_roundtrip(frame_u8, 60, subsampling="4:4:4")  # uint8 in, uint8 out
 
 ``HDRPairGenerator(jpeg_quality=...)`` applies it to the training inputs it makes.
+
+Real SDR material also carries signal-dependent sensor noise, strongest in the shadows, which a
+network that has never seen it expands into its HDR output.  ``sensor_noise`` adds the
+Poisson-Gaussian model ``e + sqrt(shot max(e, 0) + read^2) z`` to a linear image, with normals from a
+counter-based generator inside the kernel (Philox4x64-10; cnnitmo_sensor_noise, csrc/sensor_px.h), so the
+noise of an image depends on its key alone:
+
+    noisy = degrade.sensor_noise(exposure, shot=1e-3, read=2e-3, key=[7, 8, 9, 10])   # one key per image
+
+``HDRPairGenerator(response='channel', noise_shot=..., noise_read=...)`` applies the same arithmetic to
+the channel exposures in front of its camera curve.
 """
 from __future__ import annotations
 
@@ -41,6 +52,69 @@ def quant_tables(quality):
     s = 5000 // q if q < 50 else 200 - 2 * q
     base = np.array([LUMINANCE, CHROMINANCE], np.int64)
     return np.clip((base * s + 50) // 100, 1, 255).astype(np.uint16)
+
+
+def noise_keys(key, n, single=False):
+    """uint64 [n, 2]: the Philox keys of n images.  key: an int in [0, 2^64) (the key is (key, 0), for
+    every image), one int per image, or [n, 2] pairs; for a single unbatched image also one pair."""
+    k = np.asarray(key, dtype=object)
+    if k.ndim == 1 and single and k.shape[0] == 2:
+        k = k[None]
+    if k.ndim == 0:
+        k = np.array([[key, 0]] * n, dtype=object)
+    elif k.ndim == 1:
+        k = np.array([[v, 0] for v in k], dtype=object).reshape(-1, 2)
+    if k.shape != (n, 2):
+        raise ValueError(f"sensor_noise: key of shape {np.shape(key)} for {n} image(s): an int, one per image or "
+                         f"[n, 2] pairs")
+    out = np.empty((n, 2), np.uint64)
+    for i in range(n):
+        for j in range(2):
+            v = k[i, j]
+            if int(v) != v or not 0 <= int(v) < 1 << 64:
+                raise ValueError(f"sensor_noise: key word {v!r}: an integer in [0, 2^64)")
+            out[i, j] = int(v)
+    return out
+
+
+def noise_levels(shot, read, n):
+    """float64 [n, 2] = (a, b) per image from scalars or one value per image; both finite and >= 0."""
+    ab = np.empty((n, 2), np.float64)
+    for j, (name, v) in enumerate((("shot", shot), ("read", read))):
+        v = np.asarray(v, np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != n):
+            raise ValueError(f"sensor_noise: {v.shape[0] if v.ndim == 1 else v.shape} {name} values for {n} image(s)")
+        if not (np.isfinite(v).all() and (v >= 0).all()):
+            raise ValueError(f"sensor_noise: {name} {v.tolist()!r}: finite and >= 0")
+        ab[:, j] = v
+    return ab
+
+
+def sensor_noise(e, shot, read, key):
+    """Poisson-Gaussian sensor noise on a linear image: e + sqrt(shot max(e, 0) + read^2) z, unclamped,
+    with e in units of full well, ``shot`` the shot-noise factor (1 / full-well electrons) and
+    ``read`` the read-noise standard deviation.  e: fp32 [h,w,3] or [n,h,w,3], numpy array or tensor;
+    shot, read: scalars or one per image; key: see ``noise_keys``.  z are standard normals from
+    Philox4x64-10 (numpy's ``np.random.Philox``) keyed per image and counted by the pixel's index in
+    its image (cnnitmo_sensor_noise, csrc/sensor_px.h), so an image and a key give the same noise in any
+    batch, on any rank.  Returns an fp32 CUDA tensor; nothing synchronises with the host."""
+    import torch
+    from . import ops
+    t = e if isinstance(e, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(e))
+    if t.ndim not in (3, 4) or t.shape[-1] != 3 or t.numel() == 0:
+        raise ValueError(f"sensor_noise: expected [h,w,3] or [n,h,w,3], got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"sensor_noise: expected an fp32 image, got {t.dtype}")
+    single = t.ndim == 3
+    t = t.cuda().contiguous()
+    if single:
+        t = t[None]
+    n = t.shape[0]
+    ab, keys = noise_levels(shot, read, n), noise_keys(key, n, single)
+    # one upload: the levels, then the keys (8-byte items)
+    dev = torch.from_numpy(np.concatenate([ab.view(np.uint8).reshape(-1), keys.view(np.uint8).reshape(-1)])).cuda()
+    out = ops.sensor_noise(t, dev[:16 * n].view(torch.float64), dev[16 * n:].view(torch.int64))
+    return out[0] if single else out
 
 
 def jpeg_roundtrip(x, quality=75, subsampling="4:2:0"):

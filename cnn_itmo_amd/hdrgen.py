@@ -35,6 +35,13 @@ and ``last_global_batch``.  Per frame of the global batch the draws are, from th
    drawn from the stream here either: file j takes ``u = random()`` and then, for a range,
    ``q = integers(lo, hi + 1)`` from its own ``default_rng(seed + j)``, after the camera's values.
    The draw's ``'jpeg'`` is the quality, 0 for a frame that is not compressed.
+5. only with sensor noise on (``noise_shot`` or ``noise_read`` set; the stream of every generator
+   without it, with or without JPEG, is unchanged): for ``noise_shot``, then ``noise_read``, a range
+   ``(lo, hi)`` draws ``exp(log lo + random_sample() * (log hi - log lo))`` and a float draws
+   nothing; then the frame's key ``k0 = randint(0, 2**32) * 2**32 + randint(0, 2**32)`` (``k1`` is 0).
+   With ``cameras='fixed'`` file j takes the same values from its own ``default_rng(seed + j)``,
+   after the JPEG values, through ``random`` and ``integers``.  The draw's ``'noise'`` is
+   ``(a, b, k0)``, ``None`` when noise is off.
 
 The matrix handed to the kernel maps an output pixel to the source picture:
 ``M_src = T(top, left) . S . M_keras``, with ``M_keras`` the ``ImageDataGenerator.affine`` matrix at
@@ -43,6 +50,24 @@ identity when the window has the target size); the bilinear taps are clamped to 
 
 ``quantize``: ``'input'`` (default) rounds x to the 8-bit levels an SDR file has and leaves the
 target in fp32; ``'both'`` also rounds y (what the PNG route trains on); ``None`` rounds neither.
+
+``response``: ``'luminance'`` (default) is virtual_camera.m: the camera curve and the clip at 1 act on
+the luminance and the three channels share one factor, so a highlight keeps its hue however far it
+is overexposed.  ``'channel'`` exposes every channel on its own, ``e_c = key 2^v / G * hdr_c``, and
+puts each through the curve and the clip, as a sensor whose channels reach full well one after the
+other: a red lamp goes R = 1, then yellow, then white.  G is the log-average of the luminance in
+both, and the target y is the same.
+
+``noise_shot`` / ``noise_read``: ``None`` (default), a non-negative float or a range ``(lo, hi)`` with
+``0 < lo <= hi``, drawn log-uniformly per frame; either one turns sensor noise on (the other then
+counts as 0), which needs ``response='channel'``: the model lives on channel exposures.  Before the
+curve every exposure becomes ``max(0, e + sqrt(a max(e, 0) + b^2) z)`` with ``a`` the shot-noise factor
+(1 / full-well electrons), ``b`` the read-noise standard deviation in units of full well and ``z`` a
+standard normal: signal-dependent noise, strongest relative to the signal in the shadows.  ``z``
+comes from Philox4x64-10 (numpy's ``np.random.Philox``) inside the kernel, keyed by the frame's
+drawn key and counted by the pixel's index in the frame (csrc/sensor_px.h), so a frame's noise is the
+same bits on any rank, at any batch position and in any batch size.  The order is a camera's:
+noise, curve, quantisation, JPEG.  The target y carries no noise.
 
 ``jpeg_quality``: ``None`` (default) leaves x as the camera made it; an int or an inclusive range
 ``(lo, hi)`` of libjpeg qualities puts each input, with probability ``jpeg_prob``, through a
@@ -74,6 +99,22 @@ from .datagen import ImageDataGenerator, Iterator
 from .make_dataset import EXTENSIONS
 
 QUANTIZE = {None: 0, "input": 1, "both": 3}
+RESPONSES = {"luminance": 0, "channel": 1}  # cnnitmo_hdr_pairs_sensor's response
+
+
+def noise_level(name, v):
+    """None, a float >= 0 -> (v, v) or a range 0 < lo <= hi -> (lo, hi), as floats."""
+    if v is None:
+        return None
+    if np.ndim(v) == 0:
+        v = float(v)
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{name} {v!r}: a finite value >= 0")
+        return (v, v)
+    lo, hi = (float(t) for t in v)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
+        raise ValueError(f"{name} {v!r}: a range (lo, hi) with 0 < lo <= hi")
+    return (lo, hi)
 
 
 def image_size(path):
@@ -121,11 +162,13 @@ def resize_matrix(ch, cw, h, w):
 
 class HDRPairGenerator:
     """The geometric arguments are ``ImageDataGenerator``'s; ``key`` / ``lum`` those of
-    ``tonemap.reinhard`` / ``tonemap.virtual_camera``."""
+    ``tonemap.reinhard`` / ``tonemap.virtual_camera``; ``response``, ``noise_shot`` and ``noise_read``: the
+    sensor in front of the camera curve, see the module's docstring."""
 
     def __init__(self, rotation_range=0, zoom_range=0, horizontal_flip=False, vertical_flip=False, shear_range=0,
                  width_shift_range=0, height_shift_range=0, key=0.18, lum=None, quantize="input", cameras="random",
-                 jpeg_quality=None, jpeg_prob=1.0, jpeg_subsampling="4:2:0"):
+                 jpeg_quality=None, jpeg_prob=1.0, jpeg_subsampling="4:2:0", response="luminance", noise_shot=None,
+                 noise_read=None):
         if quantize not in QUANTIZE:
             raise ValueError(f"quantize {quantize!r}: 'input', 'both' or None")
         if cameras not in ("random", "fixed"):
@@ -151,6 +194,16 @@ class HDRPairGenerator:
         if jpeg_subsampling not in degrade.SUBSAMPLINGS:
             raise ValueError(f"jpeg_subsampling {jpeg_subsampling!r}: '4:4:4' or '4:2:0'")
         self.jpeg_prob, self.jpeg_subsampling = float(jpeg_prob), jpeg_subsampling
+        if response not in RESPONSES:
+            raise ValueError(f"response {response!r}: 'luminance' or 'channel'")
+        self.response = response
+        self.noise = None  # ((lo, hi) of shot, (lo, hi) of read); a range draws its value, a float does not
+        if noise_shot is not None or noise_read is not None:
+            if response != "channel":
+                raise ValueError("sensor noise is defined on channel exposures: it needs response='channel'")
+            self.noise = tuple(noise_level(k, v) or (0.0, 0.0)
+                               for k, v in (("noise_shot", noise_shot), ("noise_read", noise_read)))
+            self.noise_range = (bool(np.ndim(noise_shot)), bool(np.ndim(noise_read)))
 
     def jpeg_draw(self, uniform, integers):
         """Step 4 of a frame's draws from the two given callables: the quality, 0 = not compressed."""
@@ -158,6 +211,14 @@ class HDRPairGenerator:
         u = uniform()
         q = int(integers(lo, hi + 1)) if self.jpeg_range else lo
         return q if u < self.jpeg_prob else 0
+
+    def noise_draw(self, uniform, integers):
+        """Step 5 of a frame's draws from the two given callables: (a, b, k0)."""
+        ab = []
+        for (lo, hi), ranged in zip(self.noise, self.noise_range):
+            ab.append(float(np.exp(np.log(lo) + uniform() * (np.log(hi) - np.log(lo)))) if ranged else lo)
+        k0 = int(integers(0, 2 ** 32)) * 2 ** 32 + int(integers(0, 2 ** 32))
+        return ab[0], ab[1], k0
 
     def flow_from_directory(self, hdr_dir, target_size, window="random", window_size=None, batch_size=32,
                             shuffle=True, seed=None, cache=True, workers=8, rank=None, world=None, output="cuda",
@@ -196,15 +257,16 @@ class HDRPairIterator(Iterator):
             for f, (hs, ws) in zip(self.filenames, self.sizes):
                 if hs < ch or ws < cw:
                     raise ValueError(f"{f}: a {hs} x {ws} picture is smaller than the {ch} x {cw} window")
-        self.fixed_cameras = self.fixed_jpeg = None
+        self.fixed_cameras = self.fixed_jpeg = self.fixed_noise = None
         if gen.cameras == "fixed":
             from .tonemap import virtual_camera_params
             base = 0 if seed is None else seed
-            self.fixed_cameras, self.fixed_jpeg = [], []
+            self.fixed_cameras, self.fixed_jpeg, self.fixed_noise = [], [], []
             for j in range(len(names)):
                 own = np.random.default_rng(base + j)
                 self.fixed_cameras.append(tuple(float(a[0]) for a in virtual_camera_params(1, own)))
                 self.fixed_jpeg.append(gen.jpeg_draw(own.random, own.integers) if gen.jpeg else 0)
+                self.fixed_noise.append(gen.noise_draw(own.random, own.integers) if gen.noise else None)
         self._sources = {}
         self._pool = cf.ThreadPoolExecutor(max_workers=workers)
         self.last_draws = None
@@ -214,7 +276,8 @@ class HDRPairIterator(Iterator):
     # ---- the random stream (host only) ----------------------------------------------------
     def _draw(self, index_array):
         """The draws of every frame of the global batch, in the documented order; returns this
-        rank's share as dicts (j, params, top, left, ch, cw, camera = (v, n, y), jpeg = quality or 0)."""
+        rank's share as dicts (j, params, top, left, ch, cw, camera = (v, n, y), jpeg = quality or 0,
+        noise = (a, b, k0) or None)."""
         h, w = self.target_size
         rng, draws = self.rng, []
         for j in index_array:
@@ -242,8 +305,12 @@ class HDRPairIterator(Iterator):
             if self.gen.jpeg:
                 jpeg = self.fixed_jpeg[j] if self.fixed_jpeg is not None else \
                     self.gen.jpeg_draw(rng.random_sample, rng.randint)
+            noise = None
+            if self.gen.noise:
+                noise = self.fixed_noise[j] if self.fixed_noise is not None else \
+                    self.gen.noise_draw(rng.random_sample, rng.randint)
             draws.append({"j": j, "params": params, "top": top, "left": left, "ch": ch, "cw": cw, "camera": camera,
-                          "jpeg": jpeg})
+                          "jpeg": jpeg, "noise": noise})
         lo, hi = self._local(len(draws))
         return draws[lo:hi]
 
@@ -301,16 +368,27 @@ class HDRPairIterator(Iterator):
         mats, flips = zip(*[self.source_matrix(d) for d in draws])
         cam = np.array([[self.gen.key * 2.0 ** d["camera"][0], d["camera"][1], d["camera"][2]] for d in draws],
                        np.float64)
-        # one upload: descriptors, matrices, cameras (8-byte items), then the flips
+        # one upload: descriptors, matrices, cameras, with noise its levels and keys (8-byte items), then the flips
         parts = [desc.view(np.uint8).reshape(-1), np.stack(mats).view(np.uint8).reshape(-1),
-                 cam.view(np.uint8).reshape(-1), np.asarray(flips, np.int32).view(np.uint8)]
+                 cam.view(np.uint8).reshape(-1)]
+        if self.gen.noise:
+            parts += [np.array([d["noise"][:2] for d in draws], np.float64).view(np.uint8).reshape(-1),
+                      np.array([[d["noise"][2], 0] for d in draws], np.uint64).view(np.uint8).reshape(-1)]
+        parts.append(np.asarray(flips, np.int32).view(np.uint8))
         dev = torch.from_numpy(np.concatenate(parts)).cuda()
         cuts = np.cumsum([0] + [p.size for p in parts])
-        d_desc, d_mats, d_cam, d_flips = (dev[cuts[k]:cuts[k + 1]] for k in range(4))
+        d_desc, d_mats, d_cam, *d_noise, d_flips = (dev[cuts[k]:cuts[k + 1]] for k in range(len(parts)))
         x = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev.device)
         y = torch.empty_like(x)
-        ops.hdr_pairs(d_desc, d_mats.view(torch.float64), d_flips.view(torch.int32), d_cam.view(torch.float64), x, y,
-                      key=self.gen.key, lum=self.gen.lum, quantize=QUANTIZE[self.gen.quantize])
+        if self.gen.response == "luminance":  # noise needs 'channel'
+            ops.hdr_pairs(d_desc, d_mats.view(torch.float64), d_flips.view(torch.int32), d_cam.view(torch.float64),
+                          x, y, key=self.gen.key, lum=self.gen.lum, quantize=QUANTIZE[self.gen.quantize])
+        else:
+            d_ab, d_keys = (d_noise[0].view(torch.float64), d_noise[1].view(torch.int64)) if d_noise else (None, None)
+            ops.hdr_pairs_sensor(d_desc, d_mats.view(torch.float64), d_flips.view(torch.int32),
+                                 d_cam.view(torch.float64), x, y, key=self.gen.key, lum=self.gen.lum,
+                                 quantize=QUANTIZE[self.gen.quantize], response=RESPONSES[self.gen.response],
+                                 noise=d_ab, keys=d_keys)
         if any(d["jpeg"] for d in draws):  # in place, on x alone; the tables and the flags are host arrays
             ops.jpeg_roundtrip(x, np.stack([degrade.quant_tables(d["jpeg"] or 50) for d in draws]),
                                self.gen.jpeg_subsampling, apply=[d["jpeg"] for d in draws], out=x)

@@ -642,6 +642,58 @@ def hdr_pairs(srcs, mats, flips, cam, x, y, key=0.18, lum=None, quantize=0, warp
     return x, y
 
 
+HDR_RESPONSES = {"luminance": 0, "channel": 1}
+
+
+def _noise_pair(noise, keys, n):
+    assert noise.dtype == torch.float64 and noise.is_contiguous() and noise.numel() == 2 * n, \
+        (noise.dtype, tuple(noise.shape))
+    assert keys is not None and keys.dtype in (torch.int64, torch.uint64) and keys.is_contiguous() and \
+        keys.numel() == 2 * n, "keys: [n,2] 64-bit integers, one pair per frame"
+    assert noise.data_ptr() % 8 == 0 and keys.data_ptr() % 8 == 0
+
+
+def hdr_pairs_sensor(srcs, mats, flips, cam, x, y, key=0.18, lum=None, quantize=0, response=0, noise=None, keys=None,
+                     warped=None, logsum=None, ws=None):
+    """hdr_pairs with a sensor in front of the camera curve (cnnitmo_hdr_pairs_sensor).  response: 0 =
+    the curve on the luminance (hdr_pairs' bits), 1 = on every channel's own exposure; noise [n,2] fp64
+    = (shot factor a, read sigma b) per frame, both >= 0, None = no noise (needs response 1); keys
+    [n,2] int64 / uint64 = the frames' Philox keys, as 64-bit patterns.  All device tensors."""
+    import ctypes
+    n, h, w, _ = x.shape
+    assert srcs.dtype == torch.uint8 and srcs.numel() == n * HDR_SRC.itemsize and srcs.data_ptr() % 8 == 0
+    assert mats.dtype == torch.float64 and mats.numel() == 6 * n and flips.dtype == torch.int32 and flips.numel() == n
+    assert cam.dtype == torch.float64 and cam.numel() == 3 * n
+    for t in (x, y, warped):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, h, w, 3))
+    assert logsum is None or (logsum.dtype == torch.float64 and logsum.numel() == n)
+    if noise is not None:
+        _noise_pair(noise, keys, n)
+    if ws is None:
+        ws = workspace(hdr_pairs_workspace_bytes(n), x.device)
+    lc = None if lum is None else (ctypes.c_double * 3)(*[float(c) for c in lum])
+    call("cnnitmo_hdr_pairs_sensor", ptr(srcs), n, h, w, ptr(mats), ptr(flips),
+         None if lc is None else ctypes.addressof(lc), float(key), ptr(cam), int(quantize), int(response), ptr(noise),
+         ptr(keys) if noise is not None else None, ptr(x), ptr(y), ptr(warped), ptr(logsum), ptr(ws), ws.numel(),
+         stream_ptr())
+    return x, y
+
+
+def sensor_noise(e, noise, keys, out=None):
+    """e [n,h,w,3] contiguous fp32 device tensor -> out like e (not e itself): e + sqrt(a max(e, 0) +
+    b^2) z, unclamped (cnnitmo_sensor_noise).  noise [n,2] fp64 = (a, b) >= 0, keys [n,2] int64 / uint64:
+    device tensors; z: the Philox normals of hdr_pairs_sensor."""
+    n, h, w, c = e.shape
+    assert c == 3 and e.dtype == torch.float32 and e.is_contiguous(), (e.dtype, tuple(e.shape))
+    _noise_pair(noise, keys, n)
+    if out is None:
+        out = torch.empty_like(e)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
+    assert out.data_ptr() != e.data_ptr()
+    call("cnnitmo_sensor_noise", ptr(e), n, h, w, ptr(noise), ptr(keys), ptr(out), stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------- HDR quality metrics
 HDR_ENCODINGS = {"pq": 0, "log": 1}  # CNNITMO_ENC_*
 

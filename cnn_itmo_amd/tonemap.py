@@ -5,7 +5,8 @@ float64 arithmetic in csrc/tonemap.hip behind the C ABI.
 
   reinhard(hdr)                -> SDR   (Reinhard.m:10-24: key 0.18 / log-average)
   virtual_camera(hdr, v, n, y) -> SDR   (virtual_camera.m:10-31: exposure 2^v,
-                                         camera curve (1+n) X^y / (n + X^y), clipped at 1)
+                                         camera curve (1+n) X^y / (n + X^y), clipped at 1;
+                                         response='channel': the curve and the clip per channel)
   virtual_camera_params(count, rng)     (v ~ U[-4, 4], n ~ N(0.6, 0.1), y ~ N(0.9, 0.1))
   inverse_reinhard(sdr_u8)     -> HDR   (inverse_Reinhard.m:1-23)
   crop(img, 284, 704)                   (imcrop(image, [704 284 511 511]): a 512 x 512 window)
@@ -107,11 +108,21 @@ def virtual_camera_params(count, rng=None):
     return v, cn, cy
 
 
-def virtual_camera(hdr, v, n, y, key=0.18, lum=None, out_u8=False):
-    """virtual_camera.m: X = (key*2^v/G)*Y; X = min(1, (1+n) X^y/(n + X^y)); sdr = hdr * X/Y."""
+RESPONSES = {"luminance": 1, "channel": 1 | 16}  # cnnitmo_tonemap_apply's curve; 16 = CNNITMO_CURVE_PER_CHANNEL
+
+
+def virtual_camera(hdr, v, n, y, key=0.18, lum=None, out_u8=False, response="luminance"):
+    """virtual_camera.m: X = (key*2^v/G)*Y; X = min(1, (1+n) X^y/(n + X^y)); sdr = hdr * X/Y.
+
+    ``response='channel'`` (not in the reference) exposes and clips every channel on its own, as a
+    sensor does: X_c = (key*2^v/G)*hdr_c, sdr_c = min(1, (1+n) X_c^y/(n + X_c^y)), so an overexposed
+    colour desaturates to white where ``'luminance'`` (the default, the script) keeps its hue.  G is
+    the log-average of the luminance either way."""
+    if response not in RESPONSES:
+        raise ValueError(f"response {response!r}: 'luminance' or 'channel'")
     v, n, y = (np.atleast_1d(np.asarray(a, np.float64)) for a in (v, n, y))
     params = np.stack([key * 2.0 ** v, n, y], axis=1)
-    return _apply(1, hdr, params, lum, out_u8)
+    return _apply(RESPONSES[response], hdr, params, lum, out_u8)
 
 
 def inverse_reinhard(sdr, a=0.18, lum=None, mode="script", g=1.0):

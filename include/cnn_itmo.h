@@ -68,7 +68,9 @@ extern "C" {
  * cnnitmo_grad_sumsq / cnnitmo_grad_sumsq_workspace_bytes / cnnitmo_grad_clip,
  * cnnitmo_jpeg_roundtrip / cnnitmo_jpeg_workspace_bytes,
  * cnnitmo_resize / cnnitmo_resize_coeffs / cnnitmo_resize_workspace_bytes / cnnitmo_resize_tile_cols,
- * cnnitmo_exr_unpack / cnnitmo_exr_pack / cnnitmo_exr_workspace_bytes / cnnitmo_exr_segment_bytes. */
+ * cnnitmo_exr_unpack / cnnitmo_exr_pack / cnnitmo_exr_workspace_bytes / cnnitmo_exr_segment_bytes,
+ * cnnitmo_hdr_pairs_sensor / cnnitmo_sensor_noise (and CNNITMO_CURVE_PER_CHANNEL on curve 1 of
+ * cnnitmo_tonemap_apply, a value refused before). */
 int cnnitmo_version(void);
 const char* cnnitmo_last_error(void);
 
@@ -555,12 +557,17 @@ int cnnitmo_augment_affine(int src_u8, const void* src, int n, int h, int w, int
  *   and the count of zero-luminance pixels; f = Y (mode 0, fp32 HDR input) or
  *   X = I/(I-1) (mode 1, uint8 SDR, inverse_Reinhard.m as written).  A NaN f
  *   makes the image's sum NaN.  n <= 65535.
- *   apply: curve 0 = Reinhard, 1 = virtual camera; params (device, [n][3]) =
+ *   apply: curve 0 = Reinhard, 1 = virtual camera, 1 | CNNITMO_CURVE_PER_CHANNEL =
+ *   virtual camera with a per-channel response (X_c = key*2^v/G * hdr_c, sdr_c =
+ *   min(1, (1+n) X_c^y / (n + X_c^y)): every channel clips on its own, not in the
+ *   reference; the flag goes with curve 1 alone, any other value is refused); params
+ *   (device, [n][3]) =
  *   (key*2^v, n, y) -- Reinhard uses (0.18, -, -); out fp32 or, out_u8 = 1,
  *   imwrite's uint8(255*x).  inverse: a = the key (0.18); mode 1 = the script
  *   (uint8 sdr, stats of mode 1, g unused); mode 2 = the exact inverse of
  *   Reinhard.m for a linear fp32 sdr and the HDR log-average g (stats unused).
  */
+#define CNNITMO_CURVE_PER_CHANNEL 16 /* flag on curve 1 of cnnitmo_tonemap_apply */
 size_t cnnitmo_tonemap_workspace_bytes(int n);
 int cnnitmo_tonemap_stats(int mode, const void* img, int n, int h, int w, const double* lum_coef,
                           double* stats, void* workspace, size_t ws_bytes, void* stream);
@@ -730,6 +737,45 @@ size_t cnnitmo_hdr_pairs_workspace_bytes(int n);
 int cnnitmo_hdr_pairs(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats, const int* flips,
                       const double* lum_coef, double key, const double* cam, int quantize, float* x, float* y,
                       float* warped, double* logsum, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The same call with a sensor in front of the camera curve.  Everything above holds (same
+ * workspace, same launches, same y, warped and logsum); only x changes:
+ *   response 0: the curve acts on the luminance and the channels share its factor.  With noise
+ *     null this is the call above, bit for bit.
+ *   response 1: every channel is exposed, clipped at full well and put through the curve on its
+ *     own, so an overexposed colour goes to white as on a sensor:
+ *       e_c  = cam[i][0]/G * hdr_c                      exposure in units of full well
+ *       e'_c = max(0, noisy(e_c, a_i, b_i, z_c))        with noise, else e_c
+ *       x_c  = min(1, (1+n) e'_c^y / (n + e'_c^y))      then the store rule above
+ *     (min is fmin: a negative e_c without noise has a NaN power and gives 1.)
+ *   noise: device, [n][2] fp64 = (a, b) per frame, nullable = none; needs response 1.
+ *     noisy(e, a, b, z) = e + sqrt(a max(e, 0) + b^2) z, the Poisson-Gaussian model: a = the
+ *     shot-noise factor, b = the read-noise standard deviation, both >= 0 (the caller checks:
+ *     they live on the device).  A frame with a = b = 0 gets the bits of the call without noise.
+ *   keys: device, [n][2] uint64, required with noise.  z of pixel p = row * w + col of frame i:
+ *     (s0, s1, s2, s3) = Philox4x64-10 (Salmon et al. 2011; numpy's np.random.Philox) with
+ *     counter (p + 1, 0, 0, 0) and key keys[i], i.e. row p of np.random.Philox(key=keys[i],
+ *     counter=[0,0,0,0]).random_raw(4 h w).reshape(-1, 4).  u1 = ((s0 >> 11) + 1) 2^-53,
+ *     u2 = (s1 >> 11) 2^-53;  z_R = sqrt(-2 ln u1) cos(2 pi u2), z_G = sqrt(-2 ln u1) sin(2 pi u2);
+ *     z_B = the cosine branch on (s2, s3).  fp64, no FMA contraction.  The noise of a frame
+ *     depends on its key and its pixels alone, not on n or on its place in the batch; no
+ *     atomics, bitwise reproducible.
+ * CNNITMO_EINVAL before any device call: as above, and response outside 0..1, noise with
+ * response 0, noise without keys, noise or keys not 8-byte aligned.
+ *
+ * cnnitmo_sensor_noise: out = (float)noisy((double)e, a_i, b_i, z) for every channel value of
+ * e [n][h][w][3] fp32 (device, contiguous; out the same shape, not overlapping e), UNCLAMPED, with
+ * the z above; a frame with a = b = 0 is copied.  noise and keys as above, both required.
+ * CNNITMO_EINVAL before any device call: a null pointer, n, h or w <= 0, h*w >= 2^31,
+ * a misaligned pointer.
+ */
+int cnnitmo_hdr_pairs_sensor(const cnnitmo_hdr_src* srcs, int n, int h, int w, const double* mats, const int* flips,
+                             const double* lum_coef, double key, const double* cam, int quantize, int response,
+                             const double* noise, const uint64_t* keys, float* x, float* y, float* warped,
+                             double* logsum, void* workspace, size_t ws_bytes, void* stream);
+int cnnitmo_sensor_noise(const float* e, int n, int h, int w, const double* noise, const uint64_t* keys, float* out,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------
  * HDR quality metrics: the maps that put two linear-radiance images (fp32 [n][h][w][3],
