@@ -23,7 +23,9 @@ N = 2
 # ---- Conv2D 3x3: (cin, cout, H, W) ------------------------------------------------------------
 # halo_conv_kernel<[f32,]BN,EPI[,wres]>: BN-column blocks, EPI 1 forward / 0 input gradient,
 # wres: the block's weights stay in LDS (K <= 64 bf16 / 32 fp32 channels; K = cout for the dgrad),
-# otherwise they are streamed per 32- / 16-channel chunk.  Tiles are 16 rows x 64 columns.
+# otherwise they are streamed per 32- / 16-channel chunk.  Tiles are 16 rows x 32 columns (conv_halo.hip:
+# TH = 16, TW = 32).  These shapes have at most 24 tiles for 85 - 256 streams: no workgroup walks from
+# tile to tile here; tests/walk_cases.py holds the shapes where every workgroup does.
 CONV3X3_OPS = {  # test_gpu_ops.test_conv3x3_fwd_dgrad_wgrad
     # one partial tile
     (32, 32, 8, 12): {
@@ -45,7 +47,7 @@ CONV3X3_OPS = {  # test_gpu_ops.test_conv3x3_fwd_dgrad_wgrad
         "bf16": ("halo_conv_kernel<64,1,wres>", "halo_conv_kernel<32,0>", "wgrad_halo_kernel<64,32,64>"),
         "f32": ("halo_conv_kernel<f32,64,1,wres>", "halo_conv_kernel<f32,32,0>", "wgrad_halo_kernel<f32,64,32,64>"),
     },
-    # whole 64-column tiles, half-height (8 of 16 rows); bf16 wgrad on 128-pixel strips (w % 64 == 0)
+    # two whole 32-column tiles, half-height (8 of 16 rows); bf16 wgrad on 128-pixel strips (w % 64 == 0)
     (32, 32, 8, 64): {
         "bf16": ("halo_conv_kernel<32,1,wres>", "halo_conv_kernel<32,0,wres>", "wgrad_halo_kernel<32,32,128>"),
         "f32": ("halo_conv_kernel<f32,32,1,wres>", "halo_conv_kernel<f32,32,0,wres>", "wgrad_halo_kernel<f32,32,32,64>"),
@@ -64,12 +66,12 @@ CONV3X3_OPS = {  # test_gpu_ops.test_conv3x3_fwd_dgrad_wgrad
         "bf16": ("halo_conv_kernel<64,1,wres>", "halo_conv_kernel<64,0,wres>", "wgrad_halo_kernel<64,64,64>"),
         "f32": ("halo_conv_kernel<f32,64,1>", "halo_conv_kernel<f32,64,0>", "wgrad_halo_kernel<f32,64,64,64>"),
     },
-    # three tiles across
+    # six tiles across
     (32, 64, 12, 192): {
         "bf16": ("halo_conv_kernel<64,1,wres>", "halo_conv_kernel<32,0,wres>", "wgrad_halo_kernel<64,32,128>"),
         "f32": ("halo_conv_kernel<f32,64,1,wres>", "halo_conv_kernel<f32,32,0>", "wgrad_halo_kernel<f32,64,32,64>"),
     },
-    # whole 16 x 64 tiles
+    # whole 16 x 32 tiles
     (96, 64, 16, 128): {
         "bf16": ("halo_conv_kernel<64,1>", "halo_conv_kernel<32,0,wres>", "wgrad_halo_kernel<64,96,64>"),
         "f32": ("halo_conv_kernel<f32,64,1>", "halo_conv_kernel<f32,32,0>", "wgrad_halo_kernel<f32,64,96,64>"),
@@ -168,7 +170,7 @@ CONV3X3_FOLD = {  # test_gpu_fold.test_conv3x3_folded_fwd_wgrad (the input is a 
 }
 
 CONV3X3_ARENA = {  # test_gpu_arena.test_conv3x3
-    # one partial 16 x 64 tile; resident weights
+    # one partial 16 x 32 tile; resident weights
     (32, 32, 5, 7): {
         "bf16": ("halo_conv_kernel<32,1,wres>", "halo_conv_kernel<32,0,wres>", "wgrad_halo_kernel<32,32,64>"),
         "f32": ("halo_conv_kernel<f32,32,1,wres>", "halo_conv_kernel<f32,32,0,wres>", "wgrad_halo_kernel<f32,32,32,64>"),
@@ -386,7 +388,7 @@ DGRAD_BN = {
     # the streamed 32-column kernel (K = 128) with c0 on a block boundary: in bf16 the epilogue whose
     # blocks are each fused or plain (DGRAD_BN_BRANCH).  Its raw-buffer stores carry no tensor bound
     # (dma::brsrc: 2 GiB of records) but the in-image mask, so by hand, for the pixels m < P = 2*16*40
-    # of a 16 x 64 tile's in-image part (h = 16: no partial rows; w = 40: columns 40..63 masked):
+    # of the two 16 x 32 tiles' in-image part (h = 16: no partial rows; w = 40: columns 40..63 masked):
     #   plain block n0 = 0 -> dx element m * dx_ld + dx_off + 8g + k, 8g + k <= 31 < c0 = 32 <= the
     #     view's 160 channels: inside dx ([P][dx_ld], dx_off + 160 <= dx_ld);
     #   fused blocks n0 = 32..128 -> dz_out element m * 128 + (n0 - 32) + 8g + k <= m * 128 + 96 + 31:
