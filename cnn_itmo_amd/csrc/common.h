@@ -84,6 +84,15 @@ int cnnitmo_check_launch(const char* what);
 // Compute units of the current device (asked once); 256 when there is no device to ask.
 int cnnitmo_cu_count();
 
+// Host-side dtype dispatch: f(DType<float>{}) or f(DType<bf16>{}) by a CNNITMO_* dtype, so a
+// launcher names its kernel once:
+//   by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type; ... kernel<T> ... });
+template <typename T> struct DType { using type = T; };
+template <typename F>
+static inline auto by_dtype(int dtype, F&& f) {
+  return dtype == CNNITMO_BF16 ? f(DType<bf16>{}) : f(DType<float>{});
+}
+
 #define CNN_REQUIRE(cond, ...)                \
   do {                                        \
     if (!(cond)) {                            \
